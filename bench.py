@@ -14,17 +14,30 @@ Multi-GPU (BASELINE config 4): one process and one sim per GPU,
 4096 envs per rank (weak scaling). `--gpus N` either runs under
 torch.distributed.run (WORLD_SIZE set) or, without it, starts the N rank
 processes itself (test_isaacgym_amd/launch.py) before anything touches the GPU.
-Envs never interact, so the timed loop has no collective; at N > 1 a second leg
-times the optional RCCL all-gather of the root-state observation over xGMI
+Envs never interact, so the timed loop has no collective; at N > 1 `--full` adds
+a second leg that times the optional RCCL all-gather of the root-state observation over xGMI
 (`allgather`), and `--allgather` puts it inside the timed loop instead.
 
-Timing: W warm-up steps, a kernel-timing segment (>= 100 eager launches with
-dispatch-timestamp events), an eager segment with timing off, then the timed
-region — EXACTLY `--steps` steps replayed as hipGraphs, bracketed by barrier +
-synchronize, repeated `--repeats` times; `value` uses the median repeat of the
-per-repeat maximum over ranks.
+A plain run does only what the headline needs: set-up, W warm-up steps, the
+hipGraph capture, then the timed region — EXACTLY `--steps` steps replayed as
+hipGraphs, bracketed by barrier + synchronize — and the result line.
+`--repeats R` times R such regions back to back (default 1; 5 with `--full`);
+`value` uses the median repeat of the per-repeat maximum over ranks, and
+`ms_per_step` is that region's time over `--steps`.
 
-Prints ONE JSON line (rank 0). `roofline` prices the dominant kernel
+`--dump-outputs DIR` writes what the last timed step left in the tensors a
+caller of the loop reads (root state, rigid-body state, DOF state when the scene
+has DOFs) as DIR/<name>.npy, float32 (DIR/<name>_rank<r>.npy at N > 1). The
+scene, the action bank and the step sequence are fixed by the arguments, so two
+builds run with the same arguments can be compared array for array. Above 64 MB
+in all, a fixed seeded sample of each array's rows is written.
+
+`--full` adds everything else, as before: between the warm-up and the capture a
+kernel-timing segment (>= 100 eager launches with dispatch-timestamp events) and
+an eager segment with timing off, after the timed region the all-gather leg
+(N > 1), the secondary legs (N = 1) and the CPU baseline.
+
+Prints ONE JSON line (rank 0). With `--full`, `roofline` prices the dominant kernel
 (k_rigid_step1, one launch per simulate) at SURVEY.md §8d's algorithmic bytes:
 376 B per env per simulate (2 bodies x (state in 52 + state out 52 + mass
 properties 44 + shape 40)), plus 208 B when the refresh is fused into the step
@@ -66,6 +79,7 @@ S6_BALLS = 30
 S6_BYTES_PER_ENV = S6_BALLS * (52 + 52 + 44 + 12)
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8.0 TB/s spec
 KERNEL_TIMED_LAUNCHES = 128      # eager launches with dispatch timestamps (ring holds 256)
+DUMP_BYTES_MAX = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
 GRAPH_CHUNK_MAX = 64             # tensor-API steps captured per hipGraph at most (amortizes the graph launch)
 
 
@@ -74,7 +88,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--warmup", type=int, default=60)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; value = median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps; value = median (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-timing and eager segments (roofline), the all-gather leg (N > 1), "
+                         "the secondary legs and the CPU baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state tensors of the last step as DIR/<name>.npy")
     ap.add_argument("--envs", type=int, default=ENVS_PER_GPU, help="envs per GPU")
     ap.add_argument("--allgather", action="store_true",
                     help="RCCL all-gather of the root state inside the timed loop (N > 1)")
@@ -140,6 +160,23 @@ def capture_chunks(step, slots, chunk):
         pool = g.pool()
         graphs.append(g)
     return graphs
+
+
+def dump_outputs(path, tensors, suffix="", cap=DUMP_BYTES_MAX):
+    """--dump-outputs: every non-empty (name, tensor) as path/<name><suffix>.npy in
+    float32, whole while they fit `cap` bytes together. Above it each array keeps
+    the same fraction of its rows, drawn once with a fixed seed and kept in
+    order, so two runs with the same arguments write the same rows."""
+    import numpy as np
+    arrs = [(name, t.detach().cpu().numpy().astype(np.float32, copy=False)) for name, t in tensors if t.numel() > 0]
+    total = sum(a.nbytes for _, a in arrs)
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    for name, a in arrs:
+        if total > cap:
+            keep = max(1, int(a.shape[0] * cap / total))
+            a = a[np.sort(rng.choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def kernel_stats(sim, n_launches, run):
@@ -900,8 +937,8 @@ def main():
     gym.prepare_sim(sim)
     fuse_in_capture(sim)
     root = gymtorch.wrap_tensor(gym.acquire_actor_root_state_tensor(sim))
-    gym.acquire_rigid_body_state_tensor(sim)
-    gym.acquire_dof_state_tensor(sim)
+    rb_state = gymtorch.wrap_tensor(gym.acquire_rigid_body_state_tensor(sim))
+    dof_state = gymtorch.wrap_tensor(gym.acquire_dof_state_tensor(sim))
     chunk = graph_chunk(args.steps)
     acts = scenes.servo_actions(n, bank_slots(chunk), dev, seed=rank)
     gathered = args.allgather and world > 1
@@ -928,20 +965,23 @@ def main():
     for _ in range(args.warmup):
         step(k)
         k += 1
-    # kernel-timing segment: dispatch timestamps on, >= 100 eager launches
-    k0 = k
-    kern_ms, kmin, used = kernel_stats(sim, KERNEL_TIMED_LAUNCHES,
-                                       lambda: [step(k0 + j) for j in range(KERNEL_TIMED_LAUNCHES)])
-    k += KERNEL_TIMED_LAUNCHES
-    # eager segment, timing off: what an unmodified script's Python loop costs
-    neager = 32
-    torch.cuda.synchronize(dev)
-    t_e = time.perf_counter()
-    for _ in range(neager):
-        step(k)
-        k += 1
-    torch.cuda.synchronize(dev)
-    eager_ms = 1e3 * (time.perf_counter() - t_e) / neager
+    kern_ms = kmin = eager_ms = None
+    used = 0
+    if args.full:
+        # kernel-timing segment: dispatch timestamps on, >= 100 eager launches
+        k0 = k
+        kern_ms, kmin, used = kernel_stats(sim, KERNEL_TIMED_LAUNCHES,
+                                           lambda: [step(k0 + j) for j in range(KERNEL_TIMED_LAUNCHES)])
+        k += KERNEL_TIMED_LAUNCHES
+        # eager segment, timing off: what an unmodified script's Python loop costs
+        neager = 32
+        torch.cuda.synchronize(dev)
+        t_e = time.perf_counter()
+        for _ in range(neager):
+            step(k)
+            k += 1
+        torch.cuda.synchronize(dev)
+        eager_ms = 1e3 * (time.perf_counter() - t_e) / neager
 
     # hipGraph replay: graphs of `chunk` consecutive captured steps (step j applies
     # acts[j]), sharing one memory pool; the replayed sequence is exactly the eager
@@ -994,18 +1034,22 @@ def main():
             return [p.cpu().tolist() for p in parts]
         return [els]
 
-    reps = max(1, args.repeats)
+    reps = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     per_rank = timed(lambda r: run_steps(k + r * args.steps, args.steps), reps)
     k += reps * args.steps
     el_max = [max(per_rank[q][r] for q in range(world)) for r in range(reps)]
     el = statistics.median(el_max)
     value = world * n * args.steps / el
     ms_per_step = 1e3 * el / args.steps
+    if args.dump_outputs:
+        # the timed regions are synchronized: the tensors hold the last timed step
+        dump_outputs(args.dump_outputs, [("root_state", root), ("rigid_body_state", rb_state),
+                                         ("dof_state", dof_state)], "_rank%d" % rank if world > 1 else "")
 
     # optional RCCL all-gather of the observation (N > 1): the gather alone and
     # the eager step loop with one gather per step
     gather_leg = None
-    if world > 1 and not gathered:
+    if args.full and world > 1 and not gathered:
         gsteps = max(args.steps, 20)
         g_el = timed(lambda r: [sharding.all_gather_rows(root) for _ in range(gsteps)], 3)
         g_ms = 1e3 * statistics.median([max(g_el[q][r] for q in range(world)) for r in range(3)]) / gsteps
@@ -1052,18 +1096,22 @@ def main():
                 "repeats": reps,
                 "ms_per_step_runs": [1e3 * e / args.steps for e in el_max],
                 "ms_per_step_per_rank": [[1e3 * e / args.steps for e in row] for row in per_rank],
-                "eager_ms_per_step": eager_ms,
-                "eager_note": "eager Python loop with kernel timing off (timing is opt-in: mg_set_kernel_timing)",
                 "step_fusion": STEP_FUSION_NOTE,
             },
-            "roofline": dict(rigid_roofline(n, kern_ms, kmin, used,
-                                            "a %d-step eager segment after the warm-up" % KERNEL_TIMED_LAUNCHES),
-                             note="working set of 4096 envs (~2.8 MB) sits in L2/MALL: the step is "
-                                  "latency bound at this size (SURVEY.md §0.10); see large_n"),
+            "full": bool(args.full),
+            "dumped_outputs": args.dump_outputs,
         }
+        if args.full:
+            out["config"]["eager_ms_per_step"] = eager_ms
+            out["config"]["eager_note"] = ("eager Python loop with kernel timing off (timing is opt-in: "
+                                           "mg_set_kernel_timing)")
+            out["roofline"] = dict(rigid_roofline(n, kern_ms, kmin, used,
+                                                  "a %d-step eager segment after the warm-up" % KERNEL_TIMED_LAUNCHES),
+                                   note="working set of 4096 envs (~2.8 MB) sits in L2/MALL: the step is "
+                                        "latency bound at this size (SURVEY.md §0.10); see large_n")
         if gather_leg:
             out["allgather"] = gather_leg
-    if world == 1:
+    if world == 1 and args.full:
         # the secondary legs, each announced on stderr with its wall time (the one
         # JSON line stays the only stdout; a long default run keeps printing)
         legs = []

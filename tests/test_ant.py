@@ -1,8 +1,8 @@
 """Floating-base articulations and the MJCF importer (SURVEY.md §8f rank 2:
 assets/mjcf/nv_ant.xml as loaded by examples/apply_forces.py:67).
 
-CPU: the importer against the reference's MJCF (when /root/reference is
-present) and the repo's re-serialized copy (tools/make_ant_asset.py); oracle
+CPU: the importer against the reference's MJCF (a copy under tests/golden/)
+and the repo's re-serialized copy (tools/make_ant_asset.py); oracle
 KATs of the floating-base coupled step: exact discrete free fall, momentum
 under internal joint torques in zero gravity, the ant settling on the ground,
 the apply_forces.py vertical push. GPU: k_env_step vs the oracle bit for bit
@@ -18,7 +18,7 @@ from isaacgym import gymapi, gymtorch
 from test_isaacgym_amd import _assets, _types, scenes
 import oracle
 
-REF_ANT = "/root/reference/assets/mjcf/nv_ant.xml"
+REF_ANT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_assets", "mjcf", "nv_ant.xml")
 H = 1.0 / 60.0
 
 
@@ -46,7 +46,6 @@ def test_mjcf_ant_import():
     assert all(s.friction == 1.5 for b in a.bodies for s in b.shapes)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_ANT), reason="reference MJCF not present")
 def test_repo_ant_matches_reference_mjcf():
     a = _assets.load_mjcf(os.path.dirname(os.path.dirname(REF_ANT)), "mjcf/nv_ant.xml", _types.AssetOptions())
     b = _assets.load_mjcf(scenes.ASSET_ROOT, "mjcf/ant.xml", _types.AssetOptions())

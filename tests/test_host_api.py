@@ -87,11 +87,11 @@ def test_servo_assets_and_proxies(gym):
     # mass given, inertia missing: box inertia of the proxy at that mass
     assert np.allclose(np.diag(mp.inertia), [100 / 12 * (20 ** 2 + 3 ** 2), 100 / 12 * (16 ** 2 + 3 ** 2),
                                              100 / 12 * (16 ** 2 + 20 ** 2)])
-    ref = "/root/reference/assets"
-    if os.path.isdir(ref):   # the reference's own URDF, mesh missing -> the same frozen proxy
-        r = gym.load_asset(sim, ref, "urdf/uav/urdf/rq-1-predator-mae-uav.urdf", gymapi.AssetOptions())
-        assert r.bodies[0].shapes[0].size == uav.bodies[0].shapes[0].size
-        assert np.allclose(r.mass_props[0].inertia, mp.inertia)
+    # the reference's own URDF (a copy under tests/golden/), mesh missing -> the same frozen proxy
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_assets")
+    r = gym.load_asset(sim, ref, "urdf/uav/urdf/rq-1-predator-mae-uav.urdf", gymapi.AssetOptions())
+    assert r.bodies[0].shapes[0].size == uav.bodies[0].shapes[0].size
+    assert np.allclose(r.mass_props[0].inertia, mp.inertia)
     assert gym.load_asset(sim, scenes.ASSET_ROOT, "servo/missing.urdf", gymapi.AssetOptions()) is None
 
 

@@ -19,7 +19,6 @@ import torch
 
 from isaacgym import gymapi, gymtorch
 import oracle
-from conftest import REFERENCE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HUMANOID_DOFS = ["abdomen_z", "abdomen_y", "abdomen_x", "right_hip_x", "right_hip_z", "right_hip_y", "right_knee",
@@ -49,9 +48,9 @@ def _humanoid(gym, root):
 
 @pytest.mark.parametrize("where", ["repo", "reference"])
 def test_nv_humanoid_loads(gym, where):
-    root = os.path.join(ROOT, "assets") if where == "repo" else os.path.join(REFERENCE, "assets")
-    if where == "reference" and not os.path.exists(os.path.join(root, "mjcf", "nv_humanoid.xml")):
-        pytest.skip("reference tree absent")
+    # "reference": the reference's own file, a copy under tests/golden/
+    root = os.path.join(ROOT, "assets") if where == "repo" else os.path.join(ROOT, "tests", "golden",
+                                                                             "reference_assets")
     sim, a = _humanoid(gym, root)
     assert a is not None
     assert gym.get_asset_rigid_body_count(a) == 16 and gym.get_asset_dof_count(a) == 21

@@ -9,8 +9,8 @@
 #     probe      host facts (CPU count, affinity, cgroup quota)
 #     pytest     python -m pytest tests -m gpu (optionally -k "$3")
 #     smoke      __graft_entry__.smoke()
-#     bench      python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command)
-#     bench600   python bench.py (defaults: 600 steps)
+#     bench      python bench.py --gpus 1 --steps 20 --warmup 5 --full (the 20-step command with every leg)
+#     bench600   python bench.py (defaults: 600 steps; the headline alone, no --full)
 #     prof       rocprofv3 --kernel-trace --stats of the driver's bench command
 #     pmc        rocprofv3 FETCH_SIZE / WRITE_SIZE passes of the S1 bench (PMC_SIZES, default 4096 262144)
 #     kbench     tools/kbench.py sweep (k_rigid_step1, 2^12 .. 2^21 envs)
@@ -34,7 +34,7 @@ steps=${2:-pytest,smoke,bench,prof}
 kexpr=${3:-}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-BENCH_ARGS="--gpus 1 --steps 20 --warmup 5"
+BENCH_ARGS="--gpus 1 --steps 20 --warmup 5 --full"
 has() { [[ ",$steps," == *",$1,"* ]]; }
 if has probe; then
   { echo "nproc $(nproc)"; python -c "import os; print('cpu_count', os.cpu_count(), 'affinity', len(os.sched_getaffinity(0)))";
