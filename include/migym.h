@@ -340,6 +340,43 @@ typedef struct mg_light {
 } mg_light;
 int32_t     mg_set_light(mg_sim* sim, const mg_light* light);
 
+/* ---- rigid-body attractors ---------------------------------------------------
+ * gym.create_rigid_body_attractor / set_attractor_properties
+ * (examples/franka_attractor.py:132): an implicit 6-axis pose spring that pulls
+ * a frame fixed on one rigid body (body pose o offset) to a target pose.
+ * Axis bits 0..2 select translation along the target frame's x, y, z (at the
+ * attractor point), bits 3..5 rotation about them; stiffness and damping apply
+ * to both (N/m, N s/m; N m/rad, N m s/rad). The spring is solved implicitly in
+ * the step (h D + h^2 K joins the body's inertia), so it is stable at the
+ * script's 5e5. Supported bodies: links of articulations (uncoupled or in a
+ * coupled env) and free bodies of uncoupled envs; an attractor on a pile env's
+ * body or on a free body of a coupled env makes mg_simulate return
+ * MG_ERR_UNSUPPORTED (naming the attractor and the body) until the table is
+ * replaced. At most one attractor per body. A sim with attractors reports
+ * mg_step_out_supported 0. */
+typedef struct mg_attractor {
+    int32_t body;            /* global rigid-body index */
+    int32_t axes;            /* bits 0..5 as above */
+    float   stiffness, damping;
+    float   offset_p[3], offset_q[4];   /* attractor frame in the body frame */
+    float   target_p[3], target_q[4];   /* global coordinates (env origin added by the caller) */
+} mg_attractor;
+/* Replaces the whole table (host array; n = 0 clears it). Validates body
+ * indices (MG_ERR_ARG), finite non-negative gains (MG_ERR_ARG) and one
+ * attractor per body (MG_ERR_UNSUPPORTED); on an error the table is unchanged.
+ * The table is sent by the next mg_simulate, one asynchronous copy on its
+ * stream (not allowed while that stream is being captured into a graph).
+ * The table decides which kernels a simulate launches, so the call waits for
+ * the device and is refused (MG_ERR_STATE) when the last mg_simulate was
+ * captured into a graph, whose replays would keep the old launches: set the
+ * table before the capture, or after an eager mg_simulate. */
+int32_t     mg_set_attractors(mg_sim* sim, const mg_attractor* host, int32_t n);
+/* gym.set_attractor_target (examples/franka_attractor.py:162,168): new target
+ * poses (host, n x 7: p[3], q[4], global coordinates) of attractors
+ * first .. first + n - 1; sent by the next mg_simulate like the table. */
+int32_t     mg_set_attractor_targets(mg_sim* sim, const float* pose7_host, int32_t first, int32_t n);
+int32_t     mg_num_attractors(mg_sim* sim);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /

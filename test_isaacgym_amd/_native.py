@@ -99,6 +99,16 @@ class MgLight(ctypes.Structure):
     _fields_ = [("dir", ctypes.c_float * 3), ("color", ctypes.c_float * 3), ("ambient", ctypes.c_float * 3)]
 
 
+class MgAttractor(ctypes.Structure):
+    """mg_attractor (include/migym.h): one rigid-body attractor."""
+    _fields_ = [
+        ("body", ctypes.c_int32), ("axes", ctypes.c_int32),
+        ("stiffness", ctypes.c_float), ("damping", ctypes.c_float),
+        ("offset_p", ctypes.c_float * 3), ("offset_q", ctypes.c_float * 4),
+        ("target_p", ctypes.c_float * 3), ("target_q", ctypes.c_float * 4),
+    ]
+
+
 MG_RENDER_MAX_SHAPES = 64
 
 
@@ -160,6 +170,9 @@ def _load():
         "mg_set_light": (i32, [vp, vp]),
         "mg_last_render_ms": (ctypes.c_float, [vp]),
         "mg_cube_pick_step": (i32, [vp, vp]),
+        "mg_set_attractors": (i32, [vp, vp, i32]),
+        "mg_set_attractor_targets": (i32, [vp, vp, i32, i32]),
+        "mg_num_attractors": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -185,6 +198,7 @@ EXPORTED_SYMBOLS = (
     "mg_num_coupled_envs", "mg_num_pile_envs", "mg_fetch_host_state", "mg_host_stage", "mg_refresh_jacobian_mass_matrix",
     "mg_set_render_bodies", "mg_snapshot_render_state", "mg_render_cameras", "mg_set_light", "mg_last_render_ms",
     "mg_debug_copy_env_ctab", "mg_debug_artic_groups", "mg_step_untimed_launches", "mg_cube_pick_step", "mg_env_ctab_floats", "mg_env_carry_floats",
+    "mg_set_attractors", "mg_set_attractor_targets", "mg_num_attractors",
 )
 
 

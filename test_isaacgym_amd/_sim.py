@@ -113,7 +113,7 @@ def _warn_cross_env_contacts(A):
 
 class Env:
     __slots__ = ("sim", "index", "lower", "upper", "per_row", "origin", "actors", "num_bodies", "num_dofs",
-                 "cameras")
+                 "cameras", "attractors")
 
     def __init__(self, sim, index, lower, upper, per_row):
         self.sim = sim
@@ -133,6 +133,7 @@ class Env:
         self.num_bodies = 0
         self.num_dofs = 0
         self.cameras = []
+        self.attractors = []       # AttractorProperties, the handle is the index (create_rigid_body_attractor)
 
     def __repr__(self):
         return "Env(%d)" % self.index
@@ -252,6 +253,11 @@ class Sim:
         self.render_version = 0    # bumped by body colour / segmentation changes
         self.textures = []          # create_texture_from_file / _buffer: the handle is the index
         self.light = None           # set_light_parameters (an _native.MgLight), None: the default light
+        # rigid-body attractors (Env.attractors): the table (env-major, creation
+        # order) is sent whole by the next simulate when an attractor was created
+        # or its properties replaced, else the moved targets in one call
+        self.attr_table_dirty = False
+        self.attr_targets_dirty = set()    # (env index, handle)
 
     @property
     def renderer(self):
@@ -631,6 +637,66 @@ class Sim:
                         (2, N.lib.mg_set_dof_actuation_force)):
             c = np.ascontiguousarray(tgt[:, col])
             N.check(fn(self.native, c.ctypes.data, 1, None, 0, self.stream()), "set dof targets")
+
+    # ------------------------------------------------------------ attractors
+    def attractor_body(self, env, props):
+        """Global rigid-body index of an attractor's body (rigid_handle is an
+        env-domain body handle), or -1."""
+        self._assign_indices()
+        h = int(props.rigid_handle)
+        for a in env.actors:
+            if a.body_offset <= h < a.body_offset + a.num_bodies:
+                return a.global_body + h - a.body_offset
+        return -1
+
+    def _attractor_first(self):
+        """Table index of each env's first attractor."""
+        return np.cumsum([0] + [len(e.attractors) for e in self.envs])
+
+    @staticmethod
+    def _global_target(env, props):
+        o, t = env.origin, props.target
+        return (o[0] + t.p.x, o[1] + t.p.y, o[2] + t.p.z), (t.r.x, t.r.y, t.r.z, t.r.w)
+
+    def attractor_table(self):
+        """The packed mg_attractor table handed to mg_set_attractors: env-major,
+        creation order; targets in the global frame (env origin added)."""
+        rows = [(e, p) for e in self.envs for p in e.attractors]
+        tab = (N.MgAttractor * max(len(rows), 1))()
+        for k, (e, p) in enumerate(rows):
+            r = tab[k]
+            r.body = self.attractor_body(e, p)
+            r.axes = int(p.axes) & 63
+            r.stiffness, r.damping = float(p.stiffness), float(p.damping)
+            r.offset_p[:] = [p.offset.p.x, p.offset.p.y, p.offset.p.z]
+            r.offset_q[:] = [p.offset.r.x, p.offset.r.y, p.offset.r.z, p.offset.r.w]
+            tp, tq = self._global_target(e, p)
+            r.target_p[:] = tp
+            r.target_q[:] = tq
+        return tab, len(rows)
+
+    def push_attractors(self):
+        """Send what changed since the last simulate: the whole table, or the
+        moved targets in one mg_set_attractor_targets call."""
+        if self.native is None:
+            return
+        if self.attr_table_dirty:
+            tab, n = self.attractor_table()
+            self.attr_table_dirty = False
+            self.attr_targets_dirty.clear()
+            N.check(N.lib.mg_set_attractors(self.native, tab, n), "mg_set_attractors")
+        elif self.attr_targets_dirty:
+            first = self._attractor_first()
+            idx = sorted(int(first[e]) + h for e, h in self.attr_targets_dirty)
+            self.attr_targets_dirty.clear()
+            lo, hi = idx[0], idx[-1] + 1
+            rows = [(e, p) for e in self.envs for p in e.attractors][lo:hi]
+            pose = np.zeros((hi - lo, 7), dtype=np.float32)
+            for k, (e, p) in enumerate(rows):
+                tp, tq = self._global_target(e, p)
+                pose[k, 0:3], pose[k, 3:7] = tp, tq
+            N.check(N.lib.mg_set_attractor_targets(self.native, pose.ctypes.data, lo, hi - lo),
+                    "mg_set_attractor_targets")
 
     def require_native(self, what):
         self.finalize()

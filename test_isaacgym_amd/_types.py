@@ -123,6 +123,12 @@ RIGID_BODY_DISABLE_GRAVITY = 1
 RIGID_BODY_DISABLE_SIMULATION = 2
 
 AXIS_NONE = 0
+AXIS_X = 1
+AXIS_Y = 2
+AXIS_Z = 4
+AXIS_TWIST = 8
+AXIS_SWING_1 = 16
+AXIS_SWING_2 = 32
 AXIS_TRANSLATION = 7
 AXIS_ROTATION = 56
 AXIS_ALL = 63
@@ -531,7 +537,28 @@ class CameraProperties(_Params):
         self.enable_tensors = False
 
 
+def _as_transform(t):
+    """A Transform from a Transform or from a record of Transform.dtype (the
+    ['pose'] field of a rigid-body state, examples/franka_attractor.py:122)."""
+    if isinstance(t, Transform):
+        return Transform(t.p, t.r)
+    p, r = t["p"], t["r"]
+    return Transform(Vec3(float(p["x"]), float(p["y"]), float(p["z"])),
+                     Quat(float(r["x"]), float(r["y"]), float(r["z"]), float(r["w"])))
+
+
 class AttractorProperties(_Params):
+    """examples/franka_attractor.py:74-85. The axes select rows in the target
+    frame: AXIS_X / Y / Z translation along the target's x / y / z, AXIS_TWIST /
+    SWING_1 / SWING_2 rotation about them. target is in the env's frame (the
+    env origin is added when the table is packed), offset in the body's.
+    Assigning target or offset copies (a Transform, or the ['pose'] record of a
+    rigid-body state). Known deviation: this build's
+    get_actor_rigid_body_states returns *global* coordinates, so a target
+    copied from it (franka_attractor.py:122) carries the env origin twice for
+    an env off the origin; subtract env.origin, or set the target in the env's
+    frame."""
+
     def __init__(self):
         self.axes = AXIS_ALL
         self.damping = 0.0
@@ -539,6 +566,32 @@ class AttractorProperties(_Params):
         self.offset = Transform()
         self.rigid_handle = INVALID_HANDLE
         self.target = Transform()
+
+    @property
+    def target(self):
+        return self._target
+
+    @target.setter
+    def target(self, t):
+        self._target = _as_transform(t)
+
+    @property
+    def offset(self):
+        return self._offset
+
+    @offset.setter
+    def offset(self, t):
+        self._offset = _as_transform(t)
+
+    def __repr__(self):
+        return "AttractorProperties(axes=%r, stiffness=%r, damping=%r, rigid_handle=%r, offset=%r, target=%r)" % (
+            self.axes, self.stiffness, self.damping, self.rigid_handle, self.offset, self.target)
+
+    def copy(self):
+        c = AttractorProperties()
+        c.axes, c.stiffness, c.damping, c.rigid_handle = self.axes, self.stiffness, self.damping, self.rigid_handle
+        c.offset, c.target = self.offset, self.target
+        return c
 
 
 class TriangleMeshParams(_Params):

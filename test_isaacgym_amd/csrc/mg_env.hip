@@ -31,6 +31,7 @@
 #include "mg_collide.h"
 #include "mg_pairs.h"
 #include "mg_world.h"
+#include "mg_attractor.h"
 
 #ifdef MG_ENV_PHASE_TIMING
 // profiling build only: per-phase shader-clock cycles summed over waves
@@ -624,40 +625,57 @@ MG_HD void patch_update(Patch& R, V3 xa, Q4 qa, V3 xb, Q4 qb, const PairOut& o, 
     R = N;
 }
 
-// x = M^-1 b for a symmetric positive definite 6x6 M (row-major): left-looking
-// Cholesky, forward and backward substitution (oracle: spd6_solve_)
-MG_HD void spd6_solve(const float* M, const float* b, float* x) {
-    float Lm[36], y[6];
+// Link ln's attractor (mg_attractor.h), added by the lane that owns the link
+// before the inward pass accumulates into S.Iw: its added inertia h (D + h K)
+// sum j j^T into S.Iw[ln] and, with `bias`, its constant wrench into S.pa[ln].
+// The ABA's accelerations are relative to gravity (a0 = -g), the added inertia
+// multiplies the true one: the bias also takes M_add (0, g). S.va[ln] holds
+// the link's velocity (aba_vel) when the bias is asked for.
+template <int MAXL, int G>
+__device__ __forceinline__ void attr_link(const float* rec, EnvLds<MAXL, G>& S, int ln, V3 x0, V3 gw, float h,
+                                          bool bias) {
+    const MgAttrFrame F = attr_frame(rec, S.xl[ln], S.ql[ln], x0, h);
+    const float c = h * F.c1;
+    const V3 w = v3(S.va[ln][0], S.va[ln][1], S.va[ln][2]);
+    const V3 vO = v3(S.va[ln][3], S.va[ln][4], S.va[ln][5]);
+    // the symmetric sum (upper triangle) and the bias in registers, then one
+    // pass over the link's LDS rows
+    float Ma[21], pb[6];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float sj = M[j * 6 + j];
+    for (int e = 0; e < 21; ++e) Ma[e] = 0.0f;
 #pragma unroll
-        for (int k = 0; k < j; ++k) sj = sj - Lm[j * 6 + k] * Lm[j * 6 + k];
-        const float dj = sqrtf(sj);
-        const float inv = 1.0f / dj;
-        Lm[j * 6 + j] = dj;
+    for (int i = 0; i < 6; ++i) pb[i] = 0.0f;
 #pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            float t = M[i * 6 + j];
+    for (int k = 0; k < 6; ++k) {
+        if ((F.axes >> k) & 1) {
+            float j[6], b;
+            attr_row(F, k, w, vO, j, b);
+            const float gj = j[3] * gw.x + j[4] * gw.y + j[5] * gw.z;
+            int e = 0;
 #pragma unroll
-            for (int k = 0; k < j; ++k) t = t - Lm[i * 6 + k] * Lm[j * 6 + k];
-            Lm[i * 6 + j] = t * inv;
+            for (int i = 0; i < 6; ++i) {
+                pb[i] = pb[i] + j[i] * (c * gj - b);
+#pragma unroll
+                for (int n = i; n < 6; ++n, ++e) Ma[e] = Ma[e] + j[i] * (c * j[n]);
+            }
         }
     }
+    int e = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        float t = b[i];
+        if (bias) S.pa[ln][i] = S.pa[ln][i] + pb[i];
 #pragma unroll
-        for (int k = 0; k < i; ++k) t = t - Lm[i * 6 + k] * y[k];
-        y[i] = t / Lm[i * 6 + i];
+        for (int n = i; n < 6; ++n, ++e) {
+            S.Iw[ln][i * 6 + n] = S.Iw[ln][i * 6 + n] + Ma[e];
+            if (n > i) S.Iw[ln][n * 6 + i] = S.Iw[ln][n * 6 + i] + Ma[e];
+        }
     }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        float t = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) t = t - Lm[k * 6 + i] * x[k];
-        x[i] = t / Lm[i * 6 + i];
-    }
+}
+// the attractor record of link ln's body (body stride bs), or null
+__device__ __forceinline__ const float* attr_of(const MgEnvArgs& A, int b0, int bl, int bs) {
+    if (!A.attr_idx || bl < 0) return nullptr;
+    const int ai = A.attr_idx[b0 + bl * bs];
+    return ai >= 0 ? A.attr + (size_t)ai * MG_ATTR_N : nullptr;
 }
 
 // Articulated-body algorithm in the world frame about the base origin x0 (RBDA
@@ -680,9 +698,11 @@ MG_HD void spd6_solve(const float* M, const float* b, float* x) {
 // aba_refresh restores the world inertias and bias forces the previous inward
 // pass accumulated into, and the link velocities its outward pass overwrote
 // (recomputed: the same values bit for bit).
-template <int MAXL, int G>
+// ATTR (here and below): the attractor-aware instantiation; gw, h and the body
+// stride bs serve only it
+template <bool ATTR, int MAXL, int G>
 __device__ __forceinline__ void aba_vp(const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA, V3 x0,
-                                       const LinkC& lk, int b0) {
+                                       const LinkC& lk, int b0, V3 gw, float h, int bs) {
     // ---- velocity-product terms (lane l)
     if (act && ln < LA) {
         const int dof = A.link_i[ln * MG_LINK_I_N + 2];
@@ -707,13 +727,17 @@ __device__ __forceinline__ void aba_vp(const MgEnvArgs& A, EnvLds<MAXL, G>& S, b
         const int bl = A.link_i[ln * MG_LINK_I_N + 3];      // -1: virtual link
         if (A.ext && bl >= 0) {
             // world force f and torque t at the link COM: the wrench about x0
-            const int b = b0 + bl, nb = A.nb;
+            const int b = ATTR ? b0 + bl * bs : b0 + bl, nb = A.nb;
             const V3 f = v3(A.ext[0 * nb + b], A.ext[1 * nb + b], A.ext[2 * nb + b]);
             const V3 t = v3(A.ext[3 * nb + b], A.ext[4 * nb + b], A.ext[5 * nb + b]);
             const V3 c = vsub(vadd(S.xl[ln], qrot(S.ql[ln], lk.com)), x0);
             pb = sv(vsub(pb.w, vadd(t, vcross(c, f))), vsub(pb.v, f));
         }
         put6(S.pa[ln], pb);
+        if constexpr (ATTR) {
+            const float* rec = attr_of(A, b0, bl, bs);
+            if (rec) attr_link<MAXL, G>(rec, S, ln, x0, gw, h, true);
+        }
     }
     __syncthreads();
 }
@@ -777,9 +801,9 @@ __device__ __forceinline__ void aba_fk(const MgEnvArgs& A, SL& S, bool act, int 
     __syncthreads();
 }
 
-template <int MAXL, int G>
+template <bool ATTR, int MAXL, int G>
 __device__ __forceinline__ void aba_kin(const MgStep& P, const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA, V3 x0,
-                                        Q4 q0, const LinkC& lk, int b0, const float* poses = nullptr) {
+                                        Q4 q0, const LinkC& lk, int b0, V3 gw, int bs, const float* poses = nullptr) {
     if (poses) {
         // the link poses forward kinematics would give (MG_ENV_FK_CARRY) and the
         // joint axes from them, as aba_fk's scan forms them
@@ -814,15 +838,15 @@ __device__ __forceinline__ void aba_kin(const MgStep& P, const MgEnvArgs& A, Env
     }
     __syncthreads();
     aba_vel<MAXL, G>(A, S, act, ln, LA);
-    aba_vp<MAXL, G>(A, S, act, ln, LA, x0, lk, b0);
+    aba_vp<ATTR, MAXL, G>(A, S, act, ln, LA, x0, lk, b0, gw, P.h, bs);
 }
 
-template <int MAXL, int G>
-__device__ __forceinline__ void aba_refresh(const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA, V3 x0,
-                                            const LinkC& lk, int b0) {
+template <bool ATTR, int MAXL, int G>
+__device__ __forceinline__ void aba_refresh(const MgStep& P, const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA,
+                                            V3 x0, const LinkC& lk, int b0, V3 gw, int bs) {
     if (act && ln < LA) world_inertia(lk, S.ql[ln], S.xl[ln], x0, S.Iw[ln]);
     aba_vel<MAXL, G>(A, S, act, ln, LA);
-    aba_vp<MAXL, G>(A, S, act, ln, LA, x0, lk, b0);
+    aba_vp<ATTR, MAXL, G>(A, S, act, ln, LA, x0, lk, b0, gw, P.h, bs);
 }
 
 template <int MAXL, int G>
@@ -949,12 +973,20 @@ __device__ __forceinline__ void aba_dyn(const MgStep& P, const MgEnvArgs& A, Env
 // Called by every lane; `act` selects the envs that work. ND: static bound on D.
 // Floating base: the root slots DA..DA+5 (unit spatial axes at x0) extend the
 // matrix to NA = DA + 6: M[root r][root c] = IC_0[r][c], M[d][root r] = (IC_l xi_l)[r].
-template <int MAXL, int ND, int G>
+template <bool ATTR, int MAXL, int ND, int G>
 __device__ __forceinline__ void meff_world(const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA, int DA, V3 x0, const LinkC& lk,
-                           float (&mcol)[ND]) {
+                           float (&mcol)[ND], int b0, float h) {
     const bool fb = A.floating != 0;
     const int NA = fb ? DA + 6 : DA;
     if (act && ln < LA) world_inertia(lk, S.ql[ln], S.xl[ln], x0, S.Iw[ln]);
+    if constexpr (ATTR) {
+        // the rows see the attractor's added inertia too (the unconstrained
+        // motion was solved against it)
+        if (act && ln < LA) {
+            const float* rec = attr_of(A, b0, A.link_i[ln * MG_LINK_I_N + 3], 1);
+            if (rec) attr_link<MAXL, G>(rec, S, ln, x0, v3(0.0f, 0.0f, 0.0f), h, false);
+        }
+    }
     __syncthreads();
     if (act)
         for (int l = LA - 1; l >= 1; --l) {
@@ -1428,7 +1460,7 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
     PH_MARK(21);
 }
 
-template <int MAXL, int G>
+template <int MAXL, int G, bool ATTR>
 __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     constexpr int MAXCT = maxct<G>();
@@ -1595,11 +1627,11 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
         if (LA > 0) {
             bool xm = false, xp = false;     // this DOF runs at constant +-effort
             bool redo = live && L > 0;
-            aba_kin<MAXL, G>(P, A, S, redo, ln, LA, x0, q0, lk, b0,
-                             (MG_ENV_FK_CARRY && !first) ? cy + carry_link0<G>() : nullptr);
+            aba_kin<ATTR, MAXL, G>(P, A, S, redo, ln, LA, x0, q0, lk, b0, gw, 1,
+                                   (MG_ENV_FK_CARRY && !first) ? cy + carry_link0<G>() : nullptr);
             for (int att = 0; att < 2; ++att) {
                 if (!__any(redo)) break;
-                if (att > 0) aba_refresh<MAXL, G>(A, S, redo, ln, LA, x0, lk, b0);
+                if (att > 0) aba_refresh<ATTR, MAXL, G>(P, A, S, redo, ln, LA, x0, lk, b0, gw, 1);
                 aba_dyn<MAXL, G>(P, A, S, redo, ln, LA, x0, gw, dc, is_dof, xm, xp, b0);
                 // drives whose implicit force exceeds the effort limit
                 bool flip = false;
@@ -1726,7 +1758,7 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
 
         // ================= 3. rows
         const bool link_rows = live && S.link_rows != 0;
-        if (LA > 0 && __any(link_rows)) meff_world<MAXL, ND, G>(A, S, link_rows, ln, LA, DA, x0, lk, mcol);
+        if (LA > 0 && __any(link_rows)) meff_world<ATTR, MAXL, ND, G>(A, S, link_rows, ln, LA, DA, x0, lk, mcol, b0, h);
         PH_MARK(2);
         // this DOF lane's joint axis and origin at the substep start
         const V3 myz = S.zl[mylink], myx = S.xl[mylink];
@@ -2136,7 +2168,7 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
 // — and the link states by forward kinematics. Restated by
 // oracle/migym_oracle.c:artic_step (aba_world_ + the same integration and
 // outputs).
-template <int MAXL, int G>
+template <int MAXL, int G, bool ATTR>
 __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     __shared__ EnvLds<MAXL, G> shm[EPW];
@@ -2155,6 +2187,10 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     A.tpos_w = live ? AA.tpos_w : nullptr; A.tvel_w = live ? AA.tvel_w : nullptr; A.force_w = live ? AA.force_w : nullptr;
     const int* ai = AA.artic_i + (size_t)(live ? a : 0) * MG_ARTIC_I_N;
     const int b0 = ai[0], d0 = ai[1];
+    // link l's body is b0 + l * bs: an attractor-owning instance of a chain
+    // group keeps the group's blocked layout (row field 3, migym_capi.cpp)
+    const int bs = ATTR ? ai[3] : 1;
+    if constexpr (ATTR) { A.attr_idx = AA.attr_idx; A.attr = AA.attr; }
     const int nb = A.nb, nd = A.nd;
     const int LA = A.nl, DA = A.ndof;           // launch-uniform (barriers inside)
     const int L = live ? LA : 0, D = live ? DA : 0;
@@ -2198,7 +2234,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     const int bl = ln < LA ? A.link_i[ln * MG_LINK_I_N + 3] : -1;
     LinkC lk = {};
     lk.iq = q4(0.0f, 0.0f, 0.0f, 1.0f);
-    if (ln < L && bl >= 0) lk = load_link(A.mass, nb, b0 + bl);
+    if (ln < L && bl >= 0) lk = load_link(A.mass, nb, ATTR ? b0 + bl * bs : b0 + bl);
 
     for (int st = 0; st < P.substeps; ++st) {
         S.q[ln] = qv;
@@ -2206,10 +2242,10 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
         __syncthreads();
         bool xm = false, xp = false;     // this DOF runs at constant +-effort
         bool redo = live;
-        aba_kin<MAXL, G>(P, A, S, redo, ln, LA, x0, q0, lk, b0);
+        aba_kin<ATTR, MAXL, G>(P, A, S, redo, ln, LA, x0, q0, lk, b0, gw, bs);
         for (int att = 0; att < 2; ++att) {
             if (!__any(redo)) break;
-            if (att > 0) aba_refresh<MAXL, G>(A, S, redo, ln, LA, x0, lk, b0);
+            if (att > 0) aba_refresh<ATTR, MAXL, G>(P, A, S, redo, ln, LA, x0, lk, b0, gw, bs);
             aba_dyn<MAXL, G>(P, A, S, redo, ln, LA, x0, gw, dc, is_dof, xm, xp, b0);
             // drives whose implicit force exceeds the effort limit
             bool flip = false;
@@ -2293,7 +2329,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     }
     __syncthreads();
     if (ln < L && bl >= 0) {
-        const int b = b0 + bl;
+        const int b = ATTR ? b0 + bl * bs : b0 + bl;
         const SV vl = sv6(vs + 6 * ln);
         const Q4 ql = S.ql[ln];
         const V3 xl = S.xl[ln];
@@ -2317,17 +2353,27 @@ static bool mg_wide(int nl, int slots) { return nl > 16 || slots > 16; }
 hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
     if (!A.fixed_base || A.nl > MG_MAX_LINKS || A.ndof > MG_ENV_SLOTS_WIDE) return hipErrorNotSupported;
+    if (A.attr_idx) {
+        // instances that own an attractor (migym_capi.cpp lists them apart):
+        // the attractor-aware build, also for a group that steps in
+        // k_artic_chain otherwise
+        if (mg_wide(A.nl, A.ndof))
+            MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64, true>), dim3(A.na), dim3(64), 0, s, P, A);
+        else
+            MG_LAUNCH((k_artic_lanes<16, G16, true>), dim3((A.na + 3) / 4), dim3(64), 0, s, P, A);
+        return hipGetLastError();
+    }
     if (A.chain && A.nl >= 2 && A.nl <= 4)   // serial chain, one DOF per moving link (mg_chain.hip)
         return mg_launch_artic_chain(P, A, s);
     if (mg_wide(A.nl, A.ndof)) {
-        MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64>), dim3(A.na), dim3(64), 0, s, P, A);
+        MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64, false>), dim3(A.na), dim3(64), 0, s, P, A);
         return hipGetLastError();
     }
     const int blocks = (A.na + 3) / 4;
     if (A.nl <= 4 && A.ndof <= 4)
-        MG_LAUNCH((k_artic_lanes<4, G16>), dim3(blocks), dim3(64), 0, s, P, A);
+        MG_LAUNCH((k_artic_lanes<4, G16, false>), dim3(blocks), dim3(64), 0, s, P, A);
     else
-        MG_LAUNCH((k_artic_lanes<16, G16>), dim3(blocks), dim3(64), 0, s, P, A);
+        MG_LAUNCH((k_artic_lanes<16, G16, false>), dim3(blocks), dim3(64), 0, s, P, A);
     return hipGetLastError();
 }
 
@@ -2357,13 +2403,20 @@ hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s
         B.last = sub == P.substeps - 1 ? 1 : 0;
         if (wide) {
             MG_LAUNCH((k_env_np<MG_MAX_LINKS, 64, 64>), dim3(A.ne), dim3(64), scene, s, P, B);
-            MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64>), dim3(A.ne), dim3(64), 0, s, P, B);
+            if (A.attr_idx) MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, true>), dim3(A.ne), dim3(64), 0, s, P, B);
+            else MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, false>), dim3(A.ne), dim3(64), 0, s, P, B);
         } else if (small) {
             MG_LAUNCH((k_env_np<4, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
-            MG_LAUNCH((k_env_step<4, G16>), dim3(blocks), dim3(64), 0, s, P, B);
+            // with attractors the 16-link build steps small envs too: the two
+            // launches share only the carry and contact-table records, whose
+            // layout depends on G alone (carry_n<G>, ct_n<maxct<G>()>), not on MAXL
+            // (tests/test_attractor_gpu.py test_small_coupled_env)
+            if (A.attr_idx) MG_LAUNCH((k_env_step<16, G16, true>), dim3(blocks), dim3(64), 0, s, P, B);
+            else MG_LAUNCH((k_env_step<4, G16, false>), dim3(blocks), dim3(64), 0, s, P, B);
         } else {
             MG_LAUNCH((k_env_np<16, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
-            MG_LAUNCH((k_env_step<16, G16>), dim3(blocks), dim3(64), 0, s, P, B);
+            if (A.attr_idx) MG_LAUNCH((k_env_step<16, G16, true>), dim3(blocks), dim3(64), 0, s, P, B);
+            else MG_LAUNCH((k_env_step<16, G16, false>), dim3(blocks), dim3(64), 0, s, P, B);
         }
     }
     return hipGetLastError();

@@ -75,6 +75,10 @@ struct MgRigidArgs {
     // §3.2.1): SoA [MG_FP_N][gstride], slot b = internal slot b < nf1
     float*       gpatch;
     int          gstride;
+    // rigid-body attractors (mg_attractor.h): both null unless a free body of
+    // the launch owns one (then the attractor-aware builds step it)
+    const int*   attr_idx;    // [nb] internal slot -> record of `attr`, -1: none
+    const float* attr;        // [..][MG_ATTR_N]
 };
 
 // Articulation step arguments (lane = articulation instance).
@@ -125,6 +129,10 @@ struct MgArticArgs {
     float*       out_dof;     // [nd][2] DOF state tensor
     const int*   out_body;    // [nb] internal slot -> global body
     const int*   out_root_row;// [nb] internal slot -> actor row (-1: not a root)
+    // rigid-body attractors (mg_attractor.h): set for the launch over the
+    // instances that own one (k_artic_lanes' attractor-aware build), else null
+    const int*   attr_idx;    // [nb] internal slot -> record of `attr`, -1: none
+    const float* attr;        // [..][MG_ATTR_N]
 };
 
 // Coupled per-env step (mg_env.hip): MG_ENV_G lanes per env, one lane per
@@ -198,6 +206,10 @@ struct MgEnvArgs {
     float*       carry;       // [ne][carry] the step's state between its substep launches
     int          nhull, nshape;   // floats of the hull table, shape records (k_env_np's LDS staging)
     float*       ctab;        // [ne][ctab] this substep's contacts and anchors (k_env_np -> k_env_step)
+    // rigid-body attractors (mg_attractor.h): internal slot -> record of `attr`
+    // (-1: none); both null when no env of the launch owns one
+    const int*   attr_idx;    // [nb]
+    const float* attr;        // [..][MG_ATTR_N]
 };
 
 // Free-body pile step (mg_pile.hip): a coupled env with more

@@ -40,6 +40,7 @@
 // same specialisation, same evaluation order).
 #include "mg_internal.h"
 #include "mg_math.h"
+#include "mg_attractor.h"
 
 #ifdef MG_RIGID1_STAMPS
 // diagnostic build only (tools/kbench_rigid_stamps.py): s_memtime stamps of
@@ -325,7 +326,10 @@ __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, co
 
 // MULTI = false: bodies with one shape, static slots (candidate k -> slot k),
 // cached inertia vectors; MULTI = true: several shapes, shift-register slots.
-template <int MAXC, bool MULTI, class B>
+// ATTR: the attractor-aware build (mg_attractor.h), stepped when a free body of
+// the sim owns an attractor; a body without one runs the same operations as in
+// the plain build.
+template <int MAXC, bool MULTI, bool ATTR, class B>
 __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const MgRigidArgs& A, int b) {
     constexpr bool CACHE = !MULTI;
     const int nb = A.nb;
@@ -362,6 +366,11 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
     const float ang_keep = 1.0f - fminf(ang_damp * h, 1.0f);
     const float max_lv2 = max_lv * max_lv;
     const float max_av2 = max_av * max_av;
+    const float* at = nullptr;
+    if constexpr (ATTR) {
+        const int ai = A.attr_idx[b];
+        if (ai >= 0) at = A.attr + (size_t)ai * MG_ATTR_N;
+    }
 
     q = qnormalize(q);
     V3 fsum = v3(0.0f, 0.0f, 0.0f);
@@ -375,6 +384,9 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
         if (A.ext) {   // applied wrench this frame (uniform; none: no update, as the oracle)
             v = vmad(v, fext, invm * h);
             w = vmad(w, symmul(Iw, text), h);
+        }
+        if constexpr (ATTR) {
+            if (at) attr_free_body(at, x, q, xc, invm, invI, iq, h, v, w);
         }
         v = vscale(v, lin_keep);
         w = vscale(w, ang_keep);
@@ -732,10 +744,12 @@ __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an
 // T: this body's compact template record (MG_TREC_N floats: MG_TBODY_F_N
 // template floats, then the shape record; shape type < 0 when it has none).
 // R: the ground patch at the step's start (cnt 0: none), at its end on return.
-template <bool PACK, class B>
+// at (ATTR builds): this body's attractor record, or null.
+template <bool PACK, bool ATTR, class B>
 __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const float* T, V3& x, Q4& q, V3& v,
                                             V3& w, V3& fsum, float invm, V3 invI, Q4 iq, V3 com, bool has_ext,
-                                            V3 fext, V3 text, const float* hulls, float* gp, int gstride) {
+                                            V3 fext, V3 text, const float* hulls, float* gp, int gstride,
+                                            const float* at) {
     const float lin_damp = T[0], ang_damp = T[1], max_lv = T[2], max_av = T[3], grav_on = T[4];
     // the shape record: wide launches read it from the template record (LDS
     // when staged) in each substep's candidate search — registers are scarcer
@@ -794,6 +808,9 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
         if (has_ext) {   // applied wrench this frame (uniform; none: no update, as the oracle)
             v = vmad(v, fext, invm * h);
             w = vmad(w, symmul(Iw, text), h);
+        }
+        if constexpr (ATTR) {
+            if (at) attr_free_body(at, x, q, xc, invm, invI, iq, h, v, w);
         }
         v = vscale(v, lin_keep);
         w = vscale(w, ang_keep);
@@ -998,7 +1015,7 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
 #ifndef MG_RIGID1_WIDE_WAVES
 #define MG_RIGID1_WIDE_WAVES 3
 #endif
-template <bool UPZ, bool LDS_T, bool WIDE>
+template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR>
 __global__ void __launch_bounds__(64, UPZ && WIDE ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
 k_rigid_step1(MgStep P, MgRigidArgs A) {
     extern __shared__ float s_trec[];
@@ -1064,16 +1081,21 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     // this body's ground-patch record (slot b of the SoA [MG_FP_N][gstride] table)
     // and its LDS copy during the frame
     float* gp = live && A.gpatch ? A.gpatch + b : nullptr;
+    const float* at = nullptr;
+    if constexpr (ATTR) {
+        const int ai = A.attr_idx[b];
+        if (live && ai >= 0) at = A.attr + (size_t)ai * MG_ATTR_N;
+    }
     if constexpr (UPZ) {
-        rigid_body1<!WIDE>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text, A.hulls,
-                           gp, A.gstride);
+        rigid_body1<!WIDE, ATTR>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text,
+                                 A.hulls, gp, A.gstride, at);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        rigid_body1<!WIDE>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text, A.hulls, gp,
-                           A.gstride);
+        rigid_body1<!WIDE, ATTR>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text, A.hulls,
+                                 gp, A.gstride, at);
     }
     // the output addresses are recomputed here (an opaque copy of the slot)
     // rather than kept live in registers across the frame
@@ -1148,19 +1170,19 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     }
 }
 
-template <bool UPZ, int MAXC, bool MULTI>
+template <bool UPZ, int MAXC, bool MULTI, bool ATTR>
 __global__ void __launch_bounds__(64) k_rigid_step(MgStep P, MgRigidArgs A) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A.nf) return;
     const int b = A.free_ids ? A.free_ids[i] : i;
     if constexpr (UPZ) {
-        rigid_body<MAXC, MULTI>(BasisZ{}, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR>(BasisZ{}, P, A, b);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        rigid_body<MAXC, MULTI>(G, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR>(G, P, A, b);
     }
 }
 
@@ -1203,6 +1225,7 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         A2.body_tmpl = A.body_tmpl + A.nf1;
         A2.ext = A.ext ? A.ext + A.nf1 : nullptr;
         A2.cforce = A.cforce + A.nf1;
+        A2.attr_idx = A.attr_idx ? A.attr_idx + A.nf1 : nullptr;
     }
     if (A1.nf > 0) {
         const int blocks = (A1.nf + 63) / 64;
@@ -1215,10 +1238,17 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         const size_t lds = (size_t)A.ntb * MG_TREC_N * sizeof(float);
 #define MG_K1(U, L) \
     do { \
-        if (wide) MG_LAUNCH((k_rigid_step1<U, L, true>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
-        else MG_LAUNCH((k_rigid_step1<U, L, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
+        if (wide) MG_LAUNCH((k_rigid_step1<U, L, true, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
+        else MG_LAUNCH((k_rigid_step1<U, L, false, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
     } while (0)
-        if (lds <= MG_TREC_LDS_MAX) {
+        if (A1.attr_idx) {
+            // a free body owns an attractor: the attractor-aware builds (template
+            // records read from global memory: where they live changes no value)
+            if (upz && wide) MG_LAUNCH((k_rigid_step1<true, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+            else if (upz) MG_LAUNCH((k_rigid_step1<true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+            else if (wide) MG_LAUNCH((k_rigid_step1<false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+            else MG_LAUNCH((k_rigid_step1<false, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+        } else if (lds <= MG_TREC_LDS_MAX) {
             if (upz) MG_K1(true, true);
             else MG_K1(false, true);
         } else {
@@ -1229,8 +1259,11 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
     }
     if (A2.nf > 0) {
         const int blocks = (A2.nf + 63) / 64;
-        if (upz) MG_LAUNCH((k_rigid_step<true, MG_MAX_CONTACTS, true>), dim3(blocks), dim3(64), 0, s, P, A2);
-        else MG_LAUNCH((k_rigid_step<false, MG_MAX_CONTACTS, true>), dim3(blocks), dim3(64), 0, s, P, A2);
+        if (A2.attr_idx) {
+            if (upz) MG_LAUNCH((k_rigid_step<true, MG_MAX_CONTACTS, true, true>), dim3(blocks), dim3(64), 0, s, P, A2);
+            else MG_LAUNCH((k_rigid_step<false, MG_MAX_CONTACTS, true, true>), dim3(blocks), dim3(64), 0, s, P, A2);
+        } else if (upz) MG_LAUNCH((k_rigid_step<true, MG_MAX_CONTACTS, true, false>), dim3(blocks), dim3(64), 0, s, P, A2);
+        else MG_LAUNCH((k_rigid_step<false, MG_MAX_CONTACTS, true, false>), dim3(blocks), dim3(64), 0, s, P, A2);
     }
     return hipGetLastError();
 }

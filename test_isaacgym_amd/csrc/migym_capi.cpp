@@ -16,6 +16,7 @@
 
 #include "mg_internal.h"
 #include "mg_chainlink.h"
+#include "mg_attractor.h"
 
 thread_local MgKernelTimer* mg_timer = nullptr;
 
@@ -75,7 +76,14 @@ struct ArticGroup {
     // l, actor row or0 + a)
     int aff = 0, aff_b0 = 0, aff_d0 = 0, aff_ds = 0;
     int out_aff = 0, out_g0 = 0, out_r0 = 0;
+    // stepped instances that own an attractor (mg_set_attractors): rows
+    // step_offset .. of d_artic_split hold the other plain_count instances, then
+    // these attr_count (k_artic_lanes' attractor-aware build)
+    int attr_count = 0, plain_count = 0;
 };
+
+// what steps a body, for an attractor on it (mg_set_attractors)
+enum AttrClass : char { ATTR_NONE = 0, ATTR_FREE, ATTR_LINK, ATTR_ENV_LINK, ATTR_ENV_FREE, ATTR_PILE };
 
 // coupled envs (mg_env.hip) of one articulation template (tmpl -1: none)
 struct EnvGroup {
@@ -233,6 +241,26 @@ struct mg_sim {
     int cam_blocks = 0;
     hipEvent_t rev_b = nullptr, rev_e = nullptr;
     bool rendered = false;
+
+    // rigid-body attractors (mg_set_attractors, mg_attractor.h). The table as
+    // given; its device form (MG_ATTR_N floats per record, built in the
+    // page-locked h_attr and sent by the next simulate when attr_dirty) and
+    // the internal slot -> record map; the routing it implies: per articulation
+    // group the stepped instances with and without an attractor (d_artic_split:
+    // the group's plain rows, then its attractor rows), the counts on free
+    // bodies and coupled envs' links, and the refusal mg_simulate reports
+    std::vector<mg_attractor> attrs;
+    std::vector<char> h_body_class;       // global body -> AttrClass
+    std::vector<int> h_body_grp, h_body_inst;   // a stepped articulation's link: group, stepped instance
+    std::vector<int> h_artic_step;        // host copy of d_artic_step
+    float* d_attr = nullptr;
+    int* d_attr_idx = nullptr;            // [nb]
+    int* d_artic_split = nullptr;         // [step rows][MG_ARTIC_I_N]
+    float* h_attr = nullptr;
+    hipEvent_t attr_ev = nullptr;
+    bool attr_ev_pending = false, attr_dirty = false;
+    int n_attr_free = 0, n_attr_env = 0;
+    std::string attr_err;
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false;          // mg_set_kernel_timing: events around eager launches
@@ -521,6 +549,11 @@ void mg_destroy_sim(mg_sim* s) {
     if (s->root_ev) (void)hipEventDestroy(s->root_ev);
     if (s->h_root_in) (void)hipHostFree(s->h_root_in);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->attr_ev) (void)hipEventDestroy(s->attr_ev);
+    if (s->h_attr) (void)hipHostFree(s->h_attr);
+    if (s->d_attr) (void)hipFree(s->d_attr);
+    if (s->d_attr_idx) (void)hipFree(s->d_attr_idx);
+    if (s->d_artic_split) (void)hipFree(s->d_artic_split);
     delete s;
 }
 
@@ -937,6 +970,9 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
 
     // articulation instances grouped by template
     s->groups.clear();
+    s->h_body_class.assign(nb, ATTR_NONE);
+    s->h_body_grp.assign(nb, -1);
+    s->h_body_inst.assign(nb, -1);
     std::vector<int> artic_sorted, artic_step;
     for (int t = 0; t < m->num_artic_tmpls; ++t) {
         ArticGroup g;
@@ -1003,6 +1039,11 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
                 if (placed[ai[0] + l]) return fail(MG_ERR_ARG, "articulation %d overlaps another body", k);
                 placed[ai[0] + l] = 1;
                 if (!blk) order.push_back(ai[0] + l);
+                s->h_body_class[ai[0] + l] = cpl ? ATTR_ENV_LINK : ATTR_LINK;
+                if (!cpl) {
+                    s->h_body_grp[ai[0] + l] = (int)s->groups.size();
+                    s->h_body_inst[ai[0] + l] = g.step_count - 1;
+                }
             }
             g.count++;
         }
@@ -1085,6 +1126,11 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     for (auto& r : pile_rows)
         for (int t = 0; t < r[4]; ++t) r[5 + t] = perm[r[5 + t]];
     for (int& b : pile_body) b = perm[b];
+    for (int b = 0; b < nb; ++b)
+        if (m->body_kind[b] == MG_BODY_FREE && perm[b] < s->nf)
+            s->h_body_class[b] = perm[b] < s->nf_rigid ? ATTR_FREE : ATTR_ENV_FREE;
+    for (int slot : pile_body) s->h_body_class[order[slot]] = ATTR_PILE;
+    s->h_artic_step = artic_step;
     std::vector<int> root_int(na), tmpl_int(nb);
     for (int a = 0; a < na; ++a) root_int[a] = perm[m->actor_root_body[a]];
     for (int i = 0; i < nb; ++i) tmpl_int[i] = m->body_tmpl[order[i]];
@@ -1336,6 +1382,17 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         ~TimerScope() { mg_timer = nullptr; }
     } timer_scope;
     int slot = 0;
+    // rigid-body attractors: a table this build cannot honour is refused, never
+    // ignored; a changed table is sent here, in stream order before the step
+    if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
+    if (s->attr_dirty) {
+        if (s->capturing) return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
+        HIP_TRY(hipMemcpyAsync(s->d_attr, s->h_attr, s->attrs.size() * MG_ATTR_N * sizeof(float),
+                               hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(s->attr_ev, st));
+        s->attr_ev_pending = true;
+        s->attr_dirty = false;
+    }
     const bool timed = s->timing && !s->capturing;
     if (timed) {
         slot = (int)(s->ring_n % mg_sim::kRing);
@@ -1352,11 +1409,11 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // tensors (each one optional)
     const unsigned long long step_cid = capture_id(st);
     const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->step_out_ok &&
-                          (s->bind_root || s->bind_rb || s->bind_dof);
+                          s->attrs.empty() && (s->bind_root || s->bind_rb || s->bind_dof);
     // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
     // write into the library's own buffer, so no caller-visible tensor changes
     float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && s->step_out_ok && step_cid == 0;
+    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && step_cid == 0;
     float* ho_root = host_out ? ho_base : nullptr;
     float* ho_rb = host_out ? ho_base + (size_t)s->na * MG_STATE_N : nullptr;
     float* ho_dof = host_out && s->nd ? ho_base + (size_t)(s->na + s->nb) * MG_STATE_N : nullptr;
@@ -1388,8 +1445,27 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.out_body = s->d_slot_global;
             A.out_root_row = s->d_slot_actor;
         }
+        if (g.attr_count > 0) {
+            // instances that own an attractor step apart (the group's split rows:
+            // the plain instances, then these), rows loaded, not computed
+            A.artic_i = s->d_artic_split + (size_t)g.step_offset * MG_ARTIC_I_N;
+            A.na = g.plain_count;
+            A.aff = 0;
+            A.out_aff = 0;
+        }
         hipError_t e = mg_launch_artic_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "articulation step launch: %s", hipGetErrorString(e));
+        if (g.attr_count > 0) {
+            MgArticArgs B = A;
+            B.artic_i = A.artic_i + (size_t)g.plain_count * MG_ARTIC_I_N;
+            B.na = g.attr_count;
+            B.uni = nullptr;
+            B.attr_idx = s->d_attr_idx;
+            B.attr = s->d_attr;
+            e = mg_launch_artic_step(P, B, st);
+            if (e != hipSuccess)
+                return fail(MG_ERR_DEVICE, "articulation step launch (attractors): %s", hipGetErrorString(e));
+        }
     }
     for (const EnvGroup& g : s->env_groups) {
         MgEnvArgs A{};
@@ -1417,6 +1493,10 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.dof_props = s->d_dof_props;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
+        if (s->n_attr_env > 0) {
+            A.attr_idx = s->d_attr_idx;
+            A.attr = s->d_attr;
+        }
         hipError_t e = mg_launch_env_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
     }
@@ -1441,6 +1521,10 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.gstride = std::max(s->nf1, 1);
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
+        if (s->n_attr_free > 0) {
+            A.attr_idx = s->d_attr_idx;
+            A.attr = s->d_attr;
+        }
         bool reads_root_in = false;
         if (s->pend_root) {   // the deferred root set, read by the step kernel
             A.root_src = s->pend_root;
@@ -1569,6 +1653,153 @@ int32_t mg_set_light(mg_sim* s, const mg_light* light) {
     return MG_OK;
 }
 
+// ---- rigid-body attractors (mg_attractor.h) ----------------------------------
+// attractor a's device record
+static void attr_record(const mg_attractor& a, float* r) {
+    for (int k = 0; k < MG_ATTR_N; ++k) r[k] = 0.0f;
+    r[0] = (float)(a.axes & 63);
+    r[1] = a.stiffness;
+    r[2] = a.damping;
+    for (int k = 0; k < 3; ++k) { r[3 + k] = a.offset_p[k]; r[10 + k] = a.target_p[k]; }
+    for (int k = 0; k < 4; ++k) { r[6 + k] = a.offset_q[k]; r[13 + k] = a.target_q[k]; }
+}
+
+int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (n < 0 || (n > 0 && !host)) return fail(MG_ERR_ARG, "bad attractor table");
+    // the table decides which kernels a simulate launches: a graph captured
+    // before the call would replay the old launches
+    if (s->capturing)
+        return fail(MG_ERR_STATE, "attractor table changed after the step was captured into a graph (the replays keep "
+                    "the old launches); call it before the capture, or after an eager simulate");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<int> idx((size_t)std::max(s->nb, 1), -1);   // internal slot -> record
+    for (int i = 0; i < n; ++i) {
+        const mg_attractor& a = host[i];
+        if (a.body < 0 || a.body >= s->nb) return fail(MG_ERR_ARG, "attractor %d: body %d out of range", i, a.body);
+        if (!(std::isfinite(a.stiffness) && a.stiffness >= 0.0f && std::isfinite(a.damping) && a.damping >= 0.0f))
+            return fail(MG_ERR_ARG, "attractor %d: stiffness and damping must be finite and non-negative", i);
+        bool fin = true;
+        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(a.offset_p[k]) && std::isfinite(a.target_p[k]);
+        for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(a.offset_q[k]) && std::isfinite(a.target_q[k]);
+        if (!fin) return fail(MG_ERR_ARG, "attractor %d: offset and target must be finite", i);
+        const int slot = s->h_perm[a.body];
+        if (idx[slot] >= 0)
+            return fail(MG_ERR_UNSUPPORTED, "attractor %d: body %d already owns attractor %d (one attractor per body)",
+                        i, a.body, idx[slot]);
+        idx[slot] = i;
+    }
+    // what steps each body: the routing, or the refusal mg_simulate reports
+    std::string err;
+    int nfree = 0, nenv = 0, nartic = 0;
+    std::vector<std::vector<char>> owns(s->groups.size());
+    for (size_t gi = 0; gi < s->groups.size(); ++gi) owns[gi].assign((size_t)s->groups[gi].step_count, 0);
+    for (int i = 0; i < n; ++i) {
+        const int b = host[i].body;
+        const char* why = nullptr;
+        switch (s->h_body_class[b]) {
+            case ATTR_FREE: nfree++; break;
+            case ATTR_ENV_LINK: nenv++; break;
+            case ATTR_LINK: nartic++; owns[s->h_body_grp[b]][s->h_body_inst[b]] = 1; break;
+            case ATTR_ENV_FREE: why = "a free body of a coupled env"; break;
+            case ATTR_PILE: why = "a body of a pile env"; break;
+            default: why = "not a dynamic body"; break;
+        }
+        if (why && err.empty()) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "attractor %d on rigid body %d: %s cannot carry an attractor in this build", i, b,
+                     why);
+            err = buf;
+        }
+    }
+    // the new state is built apart — host vectors, fresh device buffers — and
+    // committed at the end, so an error leaves the sim's table as it was
+    std::vector<int> split;
+    std::vector<std::pair<int, int>> counts(s->groups.size(), {0, 0});   // plain, owners
+    if (nartic > 0) {
+        split.resize(s->h_artic_step.size());
+        for (size_t gi = 0; gi < s->groups.size(); ++gi) {
+            const ArticGroup& g = s->groups[gi];
+            int* dst = split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < g.step_count; ++k) {
+                    if ((owns[gi][k] != 0) != (pass == 1)) continue;
+                    std::memcpy(dst, s->h_artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
+                                MG_ARTIC_I_N * sizeof(int));
+                    dst += MG_ARTIC_I_N;
+                    (pass ? counts[gi].second : counts[gi].first)++;
+                }
+        }
+    }
+    struct Fresh {   // freed unless committed
+        int* idx = nullptr;
+        int* split = nullptr;
+        float* attr = nullptr;
+        float* host = nullptr;
+        ~Fresh() {
+            if (idx) (void)hipFree(idx);
+            if (split) (void)hipFree(split);
+            if (attr) (void)hipFree(attr);
+            if (host) (void)hipHostFree(host);
+        }
+    } fresh;
+    HIP_TRY(dalloc(&fresh.idx, idx.size()));
+    HIP_TRY(hipMemcpy(fresh.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!split.empty()) {
+        HIP_TRY(dalloc(&fresh.split, split.size()));
+        HIP_TRY(hipMemcpy(fresh.split, split.data(), split.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (n > 0) {
+        HIP_TRY(dalloc(&fresh.attr, (size_t)n * MG_ATTR_N));
+        HIP_TRY(hipHostMalloc((void**)&fresh.host, (size_t)n * MG_ATTR_N * sizeof(float), hipHostMallocDefault));
+        for (int i = 0; i < n; ++i) attr_record(host[i], fresh.host + (size_t)i * MG_ATTR_N);
+    }
+    if (!s->attr_ev) HIP_TRY(hipEventCreateWithFlags(&s->attr_ev, hipEventDisableTiming));
+    // no step may still read the buffers this replaces
+    HIP_TRY(hipDeviceSynchronize());
+    // ---- commit (nothing below fails)
+    s->attr_ev_pending = false;
+    std::swap(s->d_attr_idx, fresh.idx);
+    std::swap(s->d_artic_split, fresh.split);
+    std::swap(s->d_attr, fresh.attr);
+    std::swap(s->h_attr, fresh.host);
+    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
+        s->groups[gi].plain_count = counts[gi].first;
+        s->groups[gi].attr_count = counts[gi].second;
+    }
+    s->attrs.assign(host, host + n);
+    s->n_attr_free = nfree;
+    s->n_attr_env = nenv;
+    s->attr_err = err;
+    s->attr_dirty = n > 0;
+    return MG_OK;
+}
+
+int32_t mg_set_attractor_targets(mg_sim* s, const float* pose7, int32_t first, int32_t n) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (n < 0 || first < 0 || (long long)first + n > (long long)s->attrs.size() || (n > 0 && !pose7))
+        return fail(MG_ERR_ARG, "attractor targets %d .. %d out of range (%zu attractors)", first, first + n - 1,
+                    s->attrs.size());
+    for (int i = 0; i < 7 * n; ++i)
+        if (!std::isfinite(pose7[i])) return fail(MG_ERR_ARG, "attractor target %d is not finite", first + i / 7);
+    if (n == 0) return MG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->attr_ev_pending) {   // the last copy out of h_attr
+        HIP_TRY(hipEventSynchronize(s->attr_ev));
+        s->attr_ev_pending = false;
+    }
+    for (int i = 0; i < n; ++i) {
+        mg_attractor& a = s->attrs[first + i];
+        for (int k = 0; k < 3; ++k) a.target_p[k] = pose7[7 * i + k];
+        for (int k = 0; k < 4; ++k) a.target_q[k] = pose7[7 * i + 3 + k];
+        attr_record(a, s->h_attr + (size_t)(first + i) * MG_ATTR_N);
+    }
+    s->attr_dirty = true;
+    return MG_OK;
+}
+
+int32_t mg_num_attractors(mg_sim* s) { return s ? (int32_t)s->attrs.size() : 0; }
+
 float* mg_host_stage(mg_sim* s, int64_t nfloat) {
     if (!s || nfloat <= 0) { fail(MG_ERR_ARG, "null sim or empty stage"); return nullptr; }
     if (s->h_stage && s->h_stage_n >= (size_t)nfloat) return s->h_stage;
@@ -1631,7 +1862,7 @@ int32_t mg_discard_pending_sets(mg_sim* s) {
     return MG_OK;
 }
 
-int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && s->step_out_ok ? 1 : 0; }
+int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && s->step_out_ok && s->attrs.empty() ? 1 : 0; }
 
 int32_t mg_last_set_deferred(mg_sim* s) { return s ? s->last_set_deferred : 0; }
 

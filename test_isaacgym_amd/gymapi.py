@@ -154,6 +154,7 @@ class Gym:
         """One frame (test10_servo_vecenv.py:380): the fused HIP step kernels."""
         h = sim.require_native("gym.simulate")
         _check_held(sim, "simulate")
+        sim.push_attractors()
         N.check(N.lib.mg_simulate(h, sim.stream()), "mg_simulate")
         sim.held_src = []
         if sim.fusion & STEP_FUSION_STEP_OUT and "root" in sim.tensors:
@@ -165,6 +166,53 @@ class Gym:
         sim.epoch += 1
         sim.frame += 1
         sim.time += sim.params.dt
+
+    # ---- rigid-body attractors (examples/franka_attractor.py:132,158-168)
+    def create_rigid_body_attractor(self, env, props):
+        """An implicit 6-axis pose spring on one rigid body (include/migym.h
+        mg_attractor). Returns the env's attractor handle (0, 1, ... in
+        creation order), INVALID_HANDLE for an invalid rigid_handle or a body
+        that already owns an attractor."""
+        sim = env.sim
+        body = sim.attractor_body(env, props)
+        if body < 0:
+            print("*** migym: create_rigid_body_attractor: invalid rigid body handle %r" % (props.rigid_handle,),
+                  file=sys.stderr)
+            return _T.INVALID_HANDLE
+        if any(sim.attractor_body(env, p) == body for p in env.attractors):
+            print("*** migym: create_rigid_body_attractor: rigid body %r already owns an attractor (one per body)"
+                  % (props.rigid_handle,), file=sys.stderr)
+            return _T.INVALID_HANDLE
+        env.attractors.append(props.copy())
+        sim.attr_table_dirty = True
+        return len(env.attractors) - 1
+
+    def _attractor(self, env, handle):
+        if not 0 <= handle < len(env.attractors):
+            raise IndexError("invalid attractor handle %r" % (handle,))
+        return env.attractors[handle]
+
+    def get_attractor_properties(self, env, handle):
+        """A copy (examples/franka_attractor.py:158 mutates what it gets)."""
+        return self._attractor(env, handle).copy()
+
+    def set_attractor_properties(self, env, handle, props):
+        cur = self._attractor(env, handle)
+        sim = env.sim
+        body = sim.attractor_body(env, props)
+        if body < 0 or any(p is not cur and sim.attractor_body(env, p) == body for p in env.attractors):
+            print("*** migym: set_attractor_properties: invalid rigid body handle %r" % (props.rigid_handle,),
+                  file=sys.stderr)
+            return False
+        env.attractors[handle] = props.copy()
+        sim.attr_table_dirty = True
+        return True
+
+    def set_attractor_target(self, env, handle, transform):
+        """examples/franka_attractor.py:162: the target pose, in the env's frame."""
+        self._attractor(env, handle).target = transform
+        env.sim.attr_targets_dirty.add((env.index, handle))
+        return True
 
     def set_step_fusion(self, sim, flags):
         """migym extension (not in Isaac Gym): opt in to step fusion
