@@ -377,6 +377,34 @@ int32_t     mg_set_attractors(mg_sim* sim, const mg_attractor* host, int32_t n);
 int32_t     mg_set_attractor_targets(mg_sim* sim, const float* pose7_host, int32_t first, int32_t n);
 int32_t     mg_num_attractors(mg_sim* sim);
 
+/* ---- DOF force tensor ---------------------------------------------------------
+ * gym.enable_actor_dof_force_sensors / acquire_dof_force_tensor /
+ * refresh_dof_force_tensor: the force each DOF's drive applied, the mean over
+ * the frame's substeps of
+ *   POS    kp (q* - q - h u+) + kd (qd* - u+)   (q: the substep's start position,
+ *   VEL    kd (qd* - u+)                          u+: the velocity it ends with,
+ *   EFFORT the applied effort, NONE 0             after constraints and clamps)
+ * within the DOF's effort limit (a drive the effort-limit re-solve ran at the
+ * limit reports exactly +-effort). Armature, attractors, joint limits and
+ * contacts act only through u+. Computed by the step kernels themselves (their
+ * force-reporting builds, launched while at least one actor reports); DOFs of
+ * actors that do not report read 0.
+ *
+ * mg_enable_dof_forces: actor_on[a] != 0 makes actor a report (host array of
+ * n_actors = the model's actor count; NULL or all zero: nobody). Replaces the
+ * earlier choice. It decides which kernels a simulate launches, so the call
+ * waits for the device and is refused (MG_ERR_STATE) when the last mg_simulate
+ * was captured into a graph, whose replays would keep the old launches: call it
+ * before the capture, or after an eager mg_simulate.
+ * mg_refresh_dof_force: [num_dofs] floats in the API's DOF order into dst
+ * (device, or host when dst_host), as mg_refresh_dof_state. A refresh is always
+ * one small launch: the tensor is not among MG_FUSE_STEP_OUT's rows, and
+ * mg_step_out_supported is not affected by reporting.
+ * mg_num_dof_force_dofs: DOFs of the actors that report. */
+int32_t     mg_enable_dof_forces(mg_sim* sim, const int32_t* actor_on, int32_t n_actors);
+int32_t     mg_refresh_dof_force(mg_sim* sim, float* dst, int32_t dst_host, void* stream);
+int32_t     mg_num_dof_force_dofs(mg_sim* sim);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /

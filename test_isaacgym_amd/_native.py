@@ -173,6 +173,9 @@ def _load():
         "mg_set_attractors": (i32, [vp, vp, i32]),
         "mg_set_attractor_targets": (i32, [vp, vp, i32, i32]),
         "mg_num_attractors": (i32, [vp]),
+        "mg_enable_dof_forces": (i32, [vp, vp, i32]),
+        "mg_refresh_dof_force": (i32, [vp, vp, i32, vp]),
+        "mg_num_dof_force_dofs": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -199,6 +202,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_render_bodies", "mg_snapshot_render_state", "mg_render_cameras", "mg_set_light", "mg_last_render_ms",
     "mg_debug_copy_env_ctab", "mg_debug_artic_groups", "mg_step_untimed_launches", "mg_cube_pick_step", "mg_env_ctab_floats", "mg_env_carry_floats",
     "mg_set_attractors", "mg_set_attractor_targets", "mg_num_attractors",
+    "mg_enable_dof_forces", "mg_refresh_dof_force", "mg_num_dof_force_dofs",
 )
 
 

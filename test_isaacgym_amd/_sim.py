@@ -168,6 +168,7 @@ class Actor:
         # built (set_rigid_linear_velocity before prepare_sim,
         # examples/body_physics_props.py:128-130): the initial state's root row
         self.init_vel = None
+        self.dof_force_on = False     # enable_actor_dof_force_sensors
 
     @property
     def num_bodies(self):
@@ -258,6 +259,9 @@ class Sim:
         # or its properties replaced, else the moved targets in one call
         self.attr_table_dirty = False
         self.attr_targets_dirty = set()    # (env index, handle)
+        # DOF force tensor (Actor.dof_force_on): the per-actor flags are sent
+        # after the upload, and at once by a later enable
+        self.dof_force_dirty = False
 
     @property
     def renderer(self):
@@ -584,12 +588,15 @@ class Sim:
         self.tensors["rb"] = torch.from_numpy(A["body_state0"].copy()).to(dev)
         self.tensors["dof"] = torch.from_numpy(A["dof_state0"].copy()).to(dev)
         self.tensors["ncf"] = torch.zeros((self.num_bodies, 3), dtype=torch.float32, device=dev)
+        # DOF force tensor: apart from the four staged kinds (a plain copy at its refresh)
+        frc = torch.zeros((self.num_dofs,), dtype=torch.float32, device=dev)
         if dev.type == "cpu" and N.device_count() > 0 and torch.cuda.is_available():
             # the CPU pipeline's host tensors (test10's mode) in page-locked memory:
             # every refresh is a D2H copy and every set an H2D copy, which then go
             # straight over PCIe instead of through the runtime's staging buffer
             for k in ("root", "rb", "dof", "ncf"):
                 self.tensors[k] = self.tensors[k].pin_memory()
+            frc = frc.pin_memory()
             # fetch_results(sim, True) stages the whole state here in one round
             # trip (mg_fetch_host_state); the refreshes copy from it
             sizes = [self.tensors[k].numel() for k in ("root", "rb", "dof", "ncf")]
@@ -625,7 +632,18 @@ class Sim:
                 N.check(N.lib.mg_set_light(handle, ctypes.byref(self.light)), "mg_set_light")
             # actor DOF targets / props set before prepare
             self._push_dof_targets_all()
+        self.tensors["dof_force"] = frc
         self.finalized = True
+        self.push_dof_force_flags()
+
+    def push_dof_force_flags(self):
+        """Send the per-actor reporting flags (mg_enable_dof_forces) if they
+        changed since they were last sent."""
+        if self.native is None or not self.dof_force_dirty:
+            return
+        on = np.array([1 if a.dof_force_on else 0 for a in self.actors], dtype=np.int32)
+        self.dof_force_dirty = False
+        N.check(N.lib.mg_enable_dof_forces(self.native, on.ctypes.data, len(on)), "mg_enable_dof_forces")
 
     def _push_dof_targets_all(self):
         if self.num_dofs == 0:

@@ -207,6 +207,15 @@ __device__ __forceinline__ void chain_drive(const ChainDof& c, float q, float u,
     imp = im;
 }
 
+// the drive's force at the velocity w the substep ends with (from u), tau0 -
+// imp (w - u) / h with the last solve's tau0 and imp (an effort-limited DOF:
+// +-eff, imp = 0), within the effort limit
+__device__ __forceinline__ float chain_drive_force(const ChainDof& c, float tau0, float imp, float u, float w, float h) {
+    float t = tau0 - imp * ((w - u) / h);
+    if (c.eff > 0.0f) t = fminf(fmaxf(t, -c.eff), c.eff);
+    return t;
+}
+
 // (M + diag(arm + imp)) x = b by LDL^T; M given by its upper triangle M[i][j], i <= j
 template <int D>
 __device__ __forceinline__ void chain_solve(const float (&M)[D][D], const float* arm, const float* imp,
@@ -286,7 +295,9 @@ __device__ __forceinline__ void store_row(float* dst, const float (&v)[N]) {
 // (AA.uni, migym_capi.cpp; fixed after upload); UDOF: and its DOF properties
 // (wave-uniform scalar loads instead of per-lane loads and per-lane inertia
 // set-up: no VGPRs for them). s_rows / s_root: the kernel's LDS row staging.
-template <int NL, bool EXT, bool UNI, bool UDOF, bool AFF>
+// FRC: the DOF force tensor: each DOF's drive force at the
+// substep's end velocity, averaged over the frame, stored to AA.dof_frc.
+template <int NL, bool EXT, bool UNI, bool UDOF, bool AFF, bool FRC>
 __device__ __forceinline__ void chain_body(const MgStep& P, const MgArticArgs& AA, float* s_rows, float* s_root) {
     constexpr int D = NL - 1;
     const int a = blockIdx.x * 64 + threadIdx.x;
@@ -381,6 +392,11 @@ __device__ __forceinline__ void chain_body(const MgStep& P, const MgArticArgs& A
         }
     }
 
+    [[maybe_unused]] float facc[D];   // FRC: sum over the substeps of the drive forces
+    if constexpr (FRC) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) facc[d] = 0.0f;
+    }
     for (int st = 0; st < P.substeps; ++st) {
         // ---- forward: poses, axes, velocities, inertias, bias forces, and the
         // joint-space inertia accumulated link by link: link k's rigid inertia
@@ -472,6 +488,7 @@ __device__ __forceinline__ void chain_body(const MgStep& P, const MgArticArgs& A
                 if (x < dc[d].lo) { x = dc[d].lo; if (w < 0.0f) w = 0.0f; }
                 if (x > dc[d].hi) { x = dc[d].hi; if (w > 0.0f) w = 0.0f; }
             }
+            if constexpr (FRC) facc[d] += chain_drive_force(dc[d], tau0[d], imp[d], uv[d], w, h);
             qv[d] = x;
             uv[d] = w;
         }
@@ -482,6 +499,7 @@ __device__ __forceinline__ void chain_body(const MgStep& P, const MgArticArgs& A
     for (int d = 0; d < D; ++d) {
         fld(AA.dof_pos, 0, 0, d0 + d) = qv[d];
         fld(AA.dof_vel, 0, 0, d0 + d) = uv[d];
+        if constexpr (FRC) fld(AA.dof_frc, 0, 0, d0 + d) = facc[d] / (float)P.substeps;
     }
     if (AA.out_dof) {
         float o[2 * D];
@@ -736,7 +754,7 @@ __device__ __forceinline__ void chain_terms_q(const float (&ct)[D], const float 
     }
 }
 
-template <int NL, bool EXT, bool UNI, bool UDOF>
+template <int NL, bool EXT, bool UNI, bool UDOF, bool FRC>
 __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs& AA) {
     constexpr int D = NL - 1;
     CSTAMP(0);
@@ -808,6 +826,11 @@ __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs&
 
     CUSE(x0.x); CUSE(q0.w); CUSE(qv[0]); CUSE(uv[D - 1]); CUSE(dc[D - 1].tpos); CUSE(lk.m);
     CSTAMP(1);   // inputs in registers
+    [[maybe_unused]] float facc[D];   // FRC: sum over the substeps of the drive forces (every lane of the quad)
+    if constexpr (FRC) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) facc[d] = 0.0f;
+    }
     for (int st = 0; st < P.substeps; ++st) {
         SV xi[D];
         // ---- the serial scan (every lane); the values of link ml kept aside
@@ -904,6 +927,7 @@ __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs&
                 if (x < dc[d].lo) { x = dc[d].lo; if (w < 0.0f) w = 0.0f; }
                 if (x > dc[d].hi) { x = dc[d].hi; if (w > 0.0f) w = 0.0f; }
             }
+            if constexpr (FRC) facc[d] += chain_drive_force(dc[d], tau0[d], imp[d], uv[d], w, h);
             qv[d] = x;
             uv[d] = w;
         }
@@ -920,6 +944,7 @@ __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs&
         for (int d = 0; d < D; ++d) {
             fld(AA.dof_pos, 0, 0, d0 + d) = qv[d];
             fld(AA.dof_vel, 0, 0, d0 + d) = uv[d];
+            if constexpr (FRC) fld(AA.dof_frc, 0, 0, d0 + d) = facc[d] / (float)P.substeps;
         }
         if (AA.out_dof) {
             float* R = AA.out_dof + (size_t)d0 * 2;
@@ -987,13 +1012,13 @@ __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs&
 #endif
 }
 
-template <int NL, bool EXT, bool UNI>
+template <int NL, bool EXT, bool UNI, bool FRC>
 __global__ void __launch_bounds__(64, 2) k_artic_chain_q(MgStep P, MgArticArgs AA) {
     if constexpr (UNI) {
-        if (AA.uni[MG_CHAIN_UNI_DOFOK] != 0.0f) chain_body_q<NL, EXT, true, true>(P, AA);
-        else chain_body_q<NL, EXT, true, false>(P, AA);
+        if (AA.uni[MG_CHAIN_UNI_DOFOK] != 0.0f) chain_body_q<NL, EXT, true, true, FRC>(P, AA);
+        else chain_body_q<NL, EXT, true, false, FRC>(P, AA);
     } else {
-        chain_body_q<NL, EXT, false, false>(P, AA);
+        chain_body_q<NL, EXT, false, false, FRC>(P, AA);
     }
 }
 
@@ -1002,15 +1027,15 @@ __global__ void __launch_bounds__(64, 2) k_artic_chain_q(MgStep P, MgArticArgs A
 // while every instance shared them keeps stepping correctly after a
 // set_actor_dof_properties makes one differ, as the per-lane
 // path reads d_dof_props in place.
-template <int NL, bool EXT, bool UNI, bool AFF>
+template <int NL, bool EXT, bool UNI, bool AFF, bool FRC>
 __global__ void __launch_bounds__(64, MG_CHAIN_WAVES) k_artic_chain(MgStep P, MgArticArgs AA) {
     __shared__ __align__(16) float s_rows[64 * NL * MG_STATE_N];
     __shared__ __align__(16) float s_root[64 * MG_STATE_N];
     if constexpr (UNI) {
-        if (AA.uni[MG_CHAIN_UNI_DOFOK] != 0.0f) chain_body<NL, EXT, true, true, AFF>(P, AA, s_rows, s_root);
-        else chain_body<NL, EXT, true, false, AFF>(P, AA, s_rows, s_root);
+        if (AA.uni[MG_CHAIN_UNI_DOFOK] != 0.0f) chain_body<NL, EXT, true, true, AFF, FRC>(P, AA, s_rows, s_root);
+        else chain_body<NL, EXT, true, false, AFF, FRC>(P, AA, s_rows, s_root);
     } else {
-        chain_body<NL, EXT, false, false, false>(P, AA, s_rows, s_root);
+        chain_body<NL, EXT, false, false, false, FRC>(P, AA, s_rows, s_root);
     }
 }
 
@@ -1026,34 +1051,38 @@ hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStrea
 #endif
     if ((long)A.na * 4 <= MG_CHAIN_QUAD_MAX) {
         const int qb = (A.na * 4 + 63) / 64;
-#define MG_KQ(NL)                                                                                   \
-    do {                                                                                            \
-        if (A.ext) {                                                                                \
-            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, true, true>), dim3(qb), dim3(64), 0, s, P, A);  \
-            else MG_LAUNCH((k_artic_chain_q<NL, true, false>), dim3(qb), dim3(64), 0, s, P, A);       \
-        } else {                                                                                    \
-            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, false, true>), dim3(qb), dim3(64), 0, s, P, A); \
-            else MG_LAUNCH((k_artic_chain_q<NL, false, false>), dim3(qb), dim3(64), 0, s, P, A);      \
-        }                                                                                           \
+#define MG_KQ2(NL, FRC)                                                                                  \
+    do {                                                                                                 \
+        if (A.ext) {                                                                                     \
+            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, true, true, FRC>), dim3(qb), dim3(64), 0, s, P, A);  \
+            else MG_LAUNCH((k_artic_chain_q<NL, true, false, FRC>), dim3(qb), dim3(64), 0, s, P, A);       \
+        } else {                                                                                         \
+            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, false, true, FRC>), dim3(qb), dim3(64), 0, s, P, A); \
+            else MG_LAUNCH((k_artic_chain_q<NL, false, false, FRC>), dim3(qb), dim3(64), 0, s, P, A);      \
+        }                                                                                                \
     } while (0)
+    // the DOF-force builds only when the sim reports DOF forces (A.dof_frc)
+#define MG_KQ(NL) do { if (A.dof_frc) MG_KQ2(NL, true); else MG_KQ2(NL, false); } while (0)
         if (A.nl == 2) MG_KQ(2);
         else if (A.nl == 3) MG_KQ(3);
         else MG_KQ(4);
+#undef MG_KQ2
 #undef MG_KQ
         return hipGetLastError();
     }
-#define MG_KC(NL)                                                                                       \
-    do {                                                                                                \
-        if (A.ext) {                                                                                    \
-            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, true, true, true>), dim3(cb), dim3(64), 0, s, P, A);   \
-            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, true, true, false>), dim3(cb), dim3(64), 0, s, P, A);    \
-            else MG_LAUNCH((k_artic_chain<NL, true, false, false>), dim3(cb), dim3(64), 0, s, P, A);              \
-        } else {                                                                                        \
-            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, false, true, true>), dim3(cb), dim3(64), 0, s, P, A);  \
-            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, false, true, false>), dim3(cb), dim3(64), 0, s, P, A);   \
-            else MG_LAUNCH((k_artic_chain<NL, false, false, false>), dim3(cb), dim3(64), 0, s, P, A);             \
-        }                                                                                               \
+#define MG_KC2(NL, FRC)                                                                                      \
+    do {                                                                                                     \
+        if (A.ext) {                                                                                         \
+            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, true, true, true, FRC>), dim3(cb), dim3(64), 0, s, P, A);   \
+            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, true, true, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);    \
+            else MG_LAUNCH((k_artic_chain<NL, true, false, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);              \
+        } else {                                                                                             \
+            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, false, true, true, FRC>), dim3(cb), dim3(64), 0, s, P, A);  \
+            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, false, true, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);   \
+            else MG_LAUNCH((k_artic_chain<NL, false, false, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);             \
+        }                                                                                                    \
     } while (0)
+#define MG_KC(NL) do { if (A.dof_frc) MG_KC2(NL, true); else MG_KC2(NL, false); } while (0)
     // the computed-row form when the upload found the rows affine (and the
     // fused refresh's rows too, when it writes them)
     const bool aff = MG_CHAIN_AFF && A.aff && ((A.out_rb == nullptr && A.out_root == nullptr) || A.out_aff);
@@ -1061,5 +1090,6 @@ hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStrea
     else if (A.nl == 3) MG_KC(3);
     else MG_KC(4);
 #undef MG_KC
+#undef MG_KC2
     return hipGetLastError();
 }

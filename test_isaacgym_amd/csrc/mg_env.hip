@@ -849,6 +849,16 @@ __device__ __forceinline__ void aba_refresh(const MgStep& P, const MgEnvArgs& A,
     aba_vp<ATTR, MAXL, G>(A, S, act, ln, LA, x0, lk, b0, gw, P.h, bs);
 }
 
+// the DOF force tensor's term of one substep: the drive's
+// force at the velocity w the substep ends with (from u), tau0 - imp (w - u) /
+// h with the last attempt's tau0 and imp (an effort-limited DOF: +-eff, imp =
+// 0), within the effort limit
+__device__ __forceinline__ float drive_force(float eff, float tau0, float imp, float u, float w, float h) {
+    float t = tau0 - imp * ((w - u) / h);
+    if (eff > 0.0f) t = fminf(fmaxf(t, -eff), eff);
+    return t;
+}
+
 template <int MAXL, int G>
 __device__ __forceinline__ void aba_dyn(const MgStep& P, const MgEnvArgs& A, EnvLds<MAXL, G>& S, bool act, int ln, int LA, V3 x0,
                                         V3 gw, const DofC& dc, bool is_dof, bool xm, bool xp, int b0) {
@@ -1460,7 +1470,8 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
     PH_MARK(21);
 }
 
-template <int MAXL, int G, bool ATTR>
+// FRC (here and in k_artic_lanes): the build that reports the DOF force tensor
+template <int MAXL, int G, bool ATTR, bool FRC>
 __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     constexpr int MAXCT = maxct<G>();
@@ -1999,6 +2010,18 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
             if (ballr > 0) x = ball_dof_step(S.q, S.dpos, ln - (ballr - 1), ballr);
             qv = x;
             uv = w;
+            if constexpr (FRC) {
+                // the DOF force tensor: this substep's drive force at the velocity
+                // it ends with (S.u: the one it began with; S.tau0, S.imp: the last
+                // attempt's), summed on the output row from launch to launch and
+                // divided by the substep count in the last one
+                if (live) {
+                    float* fo = A.dof_frc + d0 + ln;
+                    float t = drive_force(dc.eff, S.tau0[ln], S.imp[ln], S.u[ln], w, h);
+                    if (!first) t = *fo + t;
+                    *fo = A.last ? t / (float)P.substeps : t;
+                }
+            }
         }
         __syncthreads();
         // contact impulse sums in contact order: link l on lane l, free body k on lane k
@@ -2168,7 +2191,7 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
 // — and the link states by forward kinematics. Restated by
 // oracle/migym_oracle.c:artic_step (aba_world_ + the same integration and
 // outputs).
-template <int MAXL, int G, bool ATTR>
+template <int MAXL, int G, bool ATTR, bool FRC>
 __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     __shared__ EnvLds<MAXL, G> shm[EPW];
@@ -2236,6 +2259,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     lk.iq = q4(0.0f, 0.0f, 0.0f, 1.0f);
     if (ln < L && bl >= 0) lk = load_link(A.mass, nb, ATTR ? b0 + bl * bs : b0 + bl);
 
+    [[maybe_unused]] float facc = 0.0f;   // FRC: sum over the substeps of this DOF's drive force
     for (int st = 0; st < P.substeps; ++st) {
         S.q[ln] = qv;
         S.u[ln] = uv;
@@ -2269,6 +2293,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
                 if (x > dc.hi) { x = dc.hi; if (w > 0.0f) w = 0.0f; }
             }
             S.dpos[ln] = h * w;
+            if constexpr (FRC) facc += drive_force(dc.eff, S.tau0[ln], S.imp[ln], uv, w, h);
         }
         if (any_ball) {
             __syncthreads();
@@ -2287,11 +2312,12 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     if (is_dof) {
         A.dof_pos[d0 + ln] = qv;
         A.dof_vel[d0 + ln] = uv;
+        if constexpr (FRC) AA.dof_frc[d0 + ln] = facc / (float)P.substeps;
     }
     S.q[ln] = qv;
     S.u[ln] = uv;
     __syncthreads();
-    float* vs = &S.va[0][0];          // link velocities (body frame), 6 per link
+    float* vs = &S.va[0][0];         // link velocities (body frame), 6 per link
     if (ln < L && ln > 0) {
         const float* lf = A.link_f + ln * MG_LINK_F_N;
         const int* li = A.link_i + ln * MG_LINK_I_N;
@@ -2350,6 +2376,18 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
 // MG_ENV_SLOTS_WIDE slots
 static bool mg_wide(int nl, int slots) { return nl > 16 || slots > 16; }
 
+// the force-reporting build when the launch has a DOF force row to write
+template <int MAXL, int G, bool ATTR>
+static void launch_lanes(int blocks, hipStream_t s, const MgStep& P, const MgArticArgs& A) {
+    if (A.dof_frc) MG_LAUNCH((k_artic_lanes<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    else MG_LAUNCH((k_artic_lanes<MAXL, G, ATTR, false>), dim3(blocks), dim3(64), 0, s, P, A);
+}
+template <int MAXL, int G, bool ATTR>
+static void launch_env_step(int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    if (A.dof_frc) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    else MG_LAUNCH((k_env_step<MAXL, G, ATTR, false>), dim3(blocks), dim3(64), 0, s, P, A);
+}
+
 hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
     if (!A.fixed_base || A.nl > MG_MAX_LINKS || A.ndof > MG_ENV_SLOTS_WIDE) return hipErrorNotSupported;
@@ -2358,22 +2396,22 @@ hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStrea
         // the attractor-aware build, also for a group that steps in
         // k_artic_chain otherwise
         if (mg_wide(A.nl, A.ndof))
-            MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64, true>), dim3(A.na), dim3(64), 0, s, P, A);
+            launch_lanes<MG_MAX_LINKS, 64, true>(A.na, s, P, A);
         else
-            MG_LAUNCH((k_artic_lanes<16, G16, true>), dim3((A.na + 3) / 4), dim3(64), 0, s, P, A);
+            launch_lanes<16, G16, true>((A.na + 3) / 4, s, P, A);
         return hipGetLastError();
     }
     if (A.chain && A.nl >= 2 && A.nl <= 4)   // serial chain, one DOF per moving link (mg_chain.hip)
         return mg_launch_artic_chain(P, A, s);
     if (mg_wide(A.nl, A.ndof)) {
-        MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64, false>), dim3(A.na), dim3(64), 0, s, P, A);
+        launch_lanes<MG_MAX_LINKS, 64, false>(A.na, s, P, A);
         return hipGetLastError();
     }
     const int blocks = (A.na + 3) / 4;
     if (A.nl <= 4 && A.ndof <= 4)
-        MG_LAUNCH((k_artic_lanes<4, G16, false>), dim3(blocks), dim3(64), 0, s, P, A);
+        launch_lanes<4, G16, false>(blocks, s, P, A);
     else
-        MG_LAUNCH((k_artic_lanes<16, G16, false>), dim3(blocks), dim3(64), 0, s, P, A);
+        launch_lanes<16, G16, false>(blocks, s, P, A);
     return hipGetLastError();
 }
 
@@ -2403,20 +2441,20 @@ hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s
         B.last = sub == P.substeps - 1 ? 1 : 0;
         if (wide) {
             MG_LAUNCH((k_env_np<MG_MAX_LINKS, 64, 64>), dim3(A.ne), dim3(64), scene, s, P, B);
-            if (A.attr_idx) MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, true>), dim3(A.ne), dim3(64), 0, s, P, B);
-            else MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, false>), dim3(A.ne), dim3(64), 0, s, P, B);
+            if (A.attr_idx) launch_env_step<MG_MAX_LINKS, 64, true>(A.ne, s, P, B);
+            else launch_env_step<MG_MAX_LINKS, 64, false>(A.ne, s, P, B);
         } else if (small) {
             MG_LAUNCH((k_env_np<4, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
             // with attractors the 16-link build steps small envs too: the two
             // launches share only the carry and contact-table records, whose
             // layout depends on G alone (carry_n<G>, ct_n<maxct<G>()>), not on MAXL
             // (tests/test_attractor_gpu.py test_small_coupled_env)
-            if (A.attr_idx) MG_LAUNCH((k_env_step<16, G16, true>), dim3(blocks), dim3(64), 0, s, P, B);
-            else MG_LAUNCH((k_env_step<4, G16, false>), dim3(blocks), dim3(64), 0, s, P, B);
+            if (A.attr_idx) launch_env_step<16, G16, true>(blocks, s, P, B);
+            else launch_env_step<4, G16, false>(blocks, s, P, B);
         } else {
             MG_LAUNCH((k_env_np<16, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
-            if (A.attr_idx) MG_LAUNCH((k_env_step<16, G16, true>), dim3(blocks), dim3(64), 0, s, P, B);
-            else MG_LAUNCH((k_env_step<16, G16, false>), dim3(blocks), dim3(64), 0, s, P, B);
+            if (A.attr_idx) launch_env_step<16, G16, true>(blocks, s, P, B);
+            else launch_env_step<16, G16, false>(blocks, s, P, B);
         }
     }
     return hipGetLastError();

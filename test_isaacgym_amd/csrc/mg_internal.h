@@ -133,6 +133,10 @@ struct MgArticArgs {
     // instances that own one (k_artic_lanes' attractor-aware build), else null
     const int*   attr_idx;    // [nb] internal slot -> record of `attr`, -1: none
     const float* attr;        // [..][MG_ATTR_N]
+    // DOF force tensor: [nd] each DOF's drive force, the mean
+    // over the frame's substeps; set while an actor reports DOF forces (the
+    // force-reporting builds of the step kernels), else null
+    float*       dof_frc;
 };
 
 // Coupled per-env step (mg_env.hip): MG_ENV_G lanes per env, one lane per
@@ -210,6 +214,8 @@ struct MgEnvArgs {
     // (-1: none); both null when no env of the launch owns one
     const int*   attr_idx;    // [nb]
     const float* attr;        // [..][MG_ATTR_N]
+    // DOF force tensor (MgArticArgs::dof_frc): null unless an actor reports
+    float*       dof_frc;
 };
 
 // Free-body pile step (mg_pile.hip): a coupled env with more
@@ -337,4 +343,6 @@ hipError_t mg_launch_scatter_rows(const float* aos, int ncol, const int* ids, co
                                   int n, int nrows, float* soa, int stride, hipStream_t s);
 hipError_t mg_launch_scatter_dofs(const float* aos, int ncol, const int* actor_dof, const int* sel,
                                   int nsel, int nactors, int max_dofs, float* const* dst, hipStream_t s);
+// dst[d] = on[d] != 0 ? frc[d] : 0 (the DOF force tensor's refresh)
+hipError_t mg_launch_dof_force_rows(const float* frc, const float* on, int nd, float* dst, hipStream_t s);
 hipError_t mg_launch_jacobian(const MgArticArgs& A, float* jac, float* mm, hipStream_t s);

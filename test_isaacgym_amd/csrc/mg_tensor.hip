@@ -78,6 +78,15 @@ __global__ void k_scatter_dofs(const float* __restrict__ src, int ncol, const in
     if (ncol > 1) dst1[d] = src[(long)d * ncol + 1];
 }
 
+// the DOF force tensor: the step kernels' per-DOF rows
+// (already in the API's DOF order) of the actors that report, 0 for the others
+__global__ void k_dof_force_rows(const float* __restrict__ frc, const float* __restrict__ on, int nd,
+                                 float* __restrict__ dst) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= nd) return;
+    dst[d] = on[d] != 0.0f ? frc[d] : 0.0f;
+}
+
 inline int nblocks(long total, int bs) { return (int)((total + bs - 1) / bs); }
 
 }  // namespace
@@ -106,6 +115,12 @@ hipError_t mg_launch_scatter_rows(const float* aos, int ncol, const int* ids, co
     if (ncol <= 0 || (long)n * ncol >= (1L << 31)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scatter_rows, dim3(nblocks((long)n * ncol, 256)), dim3(256), 0, s,
                        aos, ncol, ids, sel, n, nrows, soa, stride);
+    return hipGetLastError();
+}
+
+hipError_t mg_launch_dof_force_rows(const float* frc, const float* on, int nd, float* dst, hipStream_t s) {
+    if (nd <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dof_force_rows, dim3(nblocks(nd, 256)), dim3(256), 0, s, frc, on, nd, dst);
     return hipGetLastError();
 }
 

@@ -262,6 +262,13 @@ struct mg_sim {
     int n_attr_free = 0, n_attr_env = 0;
     std::string attr_err;
 
+    // DOF force tensor (mg_enable_dof_forces): the step
+    // kernels' rows [nd], then the per-DOF reporting flags [nd] the refresh
+    // applies; the force-reporting builds step while dof_frc_n > 0
+    float* d_dof_frc = nullptr;           // [2][nd]
+    std::vector<int> h_actor_dof;         // [na + 1]
+    int dof_frc_n = 0;                    // DOFs of the actors that report
+
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false;          // mg_set_kernel_timing: events around eager launches
     bool timed_step = false;      // the last simulate recorded ev_begin / ev_end
@@ -487,7 +494,7 @@ void shape_obb(const float* sh, const float* hulls, float* o) {
 
 void free_all(mg_sim* s) {
     void* ptrs[] = {s->d_state, s->d_mass, s->d_body_tmpl, s->d_free_global, s->d_perm, s->d_tbf, s->d_trec, s->d_tbi, s->d_shapes, s->d_hulls, s->d_shape_obb,
-                    s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt,
+                    s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
                     s->d_dof_props, s->d_artic, s->d_artic_step, s->d_env, s->d_pairs, s->d_fpatch, s->d_gpatch, s->d_chain_uni, s->d_fp_mask, s->d_env_carry, s->d_env_ctab, s->d_link_f, s->d_link_i, s->d_stage, s->d_stage_idx, s->d_host_out,
                     s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams};
     for (void* p : ptrs)
@@ -1159,6 +1166,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     HIP_TRY(dalloc(&s->d_dof, (size_t)nd * 2));
     HIP_TRY(dalloc(&s->d_dof_tgt, (size_t)nd * 3));
     HIP_TRY(dalloc(&s->d_dof_props, (size_t)nd * MG_DOFPROP_N));
+    HIP_TRY(dalloc(&s->d_dof_frc, (size_t)nd * 2));
     HIP_TRY(dalloc(&s->d_artic, artic_sorted.size()));
     HIP_TRY(dalloc(&s->d_artic_step, artic_step.size()));
     HIP_TRY(dalloc(&s->d_env, env_flat.size()));
@@ -1290,6 +1298,9 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     }
     HIP_TRY(h2d(s->d_actor_dof, m->actor_dof, (size_t)(na + 1) * sizeof(int)));
     HIP_TRY(hipMemset(s->d_cforce, 0, (size_t)nb * 3 * sizeof(float)));
+    HIP_TRY(hipMemset(s->d_dof_frc, 0, std::max<size_t>((size_t)nd * 2, 1) * sizeof(float)));
+    s->h_actor_dof.assign(m->actor_dof, m->actor_dof + (na > 0 ? na + 1 : 0));
+    s->dof_frc_n = 0;
     HIP_TRY(hipMemset(s->d_ext, 0, (size_t)nb * 6 * sizeof(float)));
     if (nd > 0) {
         std::vector<float> ds = to_soa(m->dof_state0, nd, 2);
@@ -1438,6 +1449,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.dof_props = s->d_dof_props;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
+        A.dof_frc = s->dof_frc_n > 0 ? s->d_dof_frc : nullptr;
         if (step_out || host_out) {   // chain groups only (s->step_out_ok)
             A.out_rb = step_out ? s->bind_rb : ho_rb;
             A.out_root = step_out ? s->bind_root : ho_root;
@@ -1493,6 +1505,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.dof_props = s->d_dof_props;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
+        A.dof_frc = s->dof_frc_n > 0 ? s->d_dof_frc : nullptr;
         if (s->n_attr_env > 0) {
             A.attr_idx = s->d_attr_idx;
             A.attr = s->d_attr;
@@ -2013,6 +2026,53 @@ int32_t mg_refresh_dof_state(mg_sim* s, float* dst, int32_t dst_host, void* stre
         return MG_OK;   // written by the step kernel (MG_FUSE_STEP_OUT)
     return refresh_rows(s, s->d_dof, s->nd, 2, nullptr, s->nd, dst, dst_host, (hipStream_t)stream);
 }
+
+// ---- DOF force tensor --------------------------------------
+int32_t mg_enable_dof_forces(mg_sim* s, const int32_t* actor_on, int32_t n_actors) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (actor_on && n_actors != s->na)
+        return fail(MG_ERR_ARG, "DOF force flags for %d actors, the model has %d", n_actors, s->na);
+    // the flags decide which kernels a simulate launches: a graph captured
+    // before the call would replay the old launches
+    if (s->capturing)
+        return fail(MG_ERR_STATE, "DOF force reporting changed after the step was captured into a graph (the replays "
+                    "keep the old launches); call it before the capture, or after an eager simulate");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<float> on((size_t)std::max(s->nd, 1), 0.0f);
+    int n = 0;
+    if (actor_on)
+        for (int a = 0; a < s->na; ++a)
+            if (actor_on[a])
+                for (int d = s->h_actor_dof[a]; d < s->h_actor_dof[a + 1]; ++d) { on[d] = 1.0f; ++n; }
+    // rows of actors that stop reporting, or that no kernel steps, read 0
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(s->d_dof_frc, 0, (size_t)std::max(s->nd, 1) * sizeof(float)));
+    if (s->nd > 0)
+        HIP_TRY(hipMemcpy(s->d_dof_frc + s->nd, on.data(), (size_t)s->nd * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    s->dof_frc_n = n;
+    return MG_OK;
+}
+
+int32_t mg_refresh_dof_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (!dst && s->nd > 0) return fail(MG_ERR_ARG, "null destination");
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->nd == 0) return MG_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!dst_host) {
+        HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->nd, s->nd, dst, st));
+        return MG_OK;
+    }
+    if (int rc = ensure_stage(s, (size_t)s->nd, 0)) return rc;
+    HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->nd, s->nd, s->d_stage, st));
+    HIP_TRY(hipMemcpyAsync(dst, s->d_stage, (size_t)s->nd * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MG_OK;
+}
+
+int32_t mg_num_dof_force_dofs(mg_sim* s) { return s ? s->dof_frc_n : 0; }
+
 int32_t mg_refresh_net_contact_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
     return refresh_rows(s, s->d_cforce, s->nb, 3, s->d_perm, s->nb, dst, dst_host, (hipStream_t)stream);

@@ -1037,6 +1037,57 @@ class Gym:
     def refresh_net_contact_force_tensor(self, sim):
         return self._refresh(sim, "ncf", N.lib.mg_refresh_net_contact_force, "refresh_net_contact_force_tensor")
 
+    # ---- DOF force tensor (include/migym.h)
+    def enable_actor_dof_force_sensors(self, env, handle):
+        """The actor's DOFs report their drive forces in the DOF force tensor
+        (the other actors' DOFs read 0). Before prepare_sim or the first
+        simulate: it chooses the step kernels' force-reporting builds."""
+        a = self._actor(env, handle)
+        sim = env.sim
+        if a.num_dofs == 0:
+            print("*** migym: enable_actor_dof_force_sensors: actor %r has no DOFs" % (a.name,), file=sys.stderr)
+            return False
+        if sim.frame > 0:
+            print("*** migym: enable_actor_dof_force_sensors: call it before the first simulate", file=sys.stderr)
+            return False
+        if not a.dof_force_on:
+            a.dof_force_on = True
+            sim.dof_force_dirty = True
+            if sim.finalized:       # after prepare_sim: sent now (finalize sends the earlier ones)
+                try:
+                    sim.push_dof_force_flags()
+                except N.MigymError as e:
+                    a.dof_force_on = False
+                    print("*** migym: enable_actor_dof_force_sensors: %s" % e, file=sys.stderr)
+                    return False
+        return True
+
+    def acquire_dof_force_tensor(self, sim):
+        """(num_dofs,) float32, the API's DOF order; the same storage on every call."""
+        return self._acquire(sim, "dof_force")
+
+    def refresh_dof_force_tensor(self, sim):
+        sim.finalize()
+        t = sim.tensors["dof_force"]
+        if t.numel() == 0:
+            return True
+        h = sim.require_native("refresh_dof_force_tensor")
+        N.check(N.lib.mg_refresh_dof_force(h, t.data_ptr(), 1 if t.device.type == "cpu" else 0, sim.stream()),
+                "refresh_dof_force_tensor")
+        return True
+
+    def get_actor_dof_forces(self, env, handle):
+        """The actor's rows of the DOF force tensor (float32 numpy array)."""
+        a = self._actor(env, handle)
+        sim = env.sim
+        out = np.zeros(a.num_dofs, dtype=np.float32)
+        if not sim.finalized or sim.native is None or sim.num_dofs == 0:
+            return out
+        full = np.zeros(sim.num_dofs, dtype=np.float32)
+        N.check(N.lib.mg_refresh_dof_force(sim.native, full.ctypes.data, 1, sim.stream()), "mg_refresh_dof_force")
+        out[:] = full[a.global_dof:a.global_dof + a.num_dofs]
+        return out
+
     def _set(self, sim, tensor, fn, ncols, nrows, what, index=None, count=None):
         sim.finalize()
         sim.epoch += 1
