@@ -46,6 +46,14 @@ struct MgStep {
 #define MG_TREC_LDS_MAX  (48 * 1024)
 #endif
 
+// Every static per-slot index of the single-shape free-body step in one 16-byte
+// record (slot b at index b), so that a one-round launch fetches them with one
+// load beside its other inputs (k_rigid_step1): the values of
+// MgRigidArgs::root_row, body_tmpl, out_body and out_root_row.
+struct alignas(16) MgSlotRec {
+    int root_row, body_tmpl, out_body, out_root_row;
+};
+
 // Kernel argument block of the free-body step (SoA arrays, stride = nb).
 struct MgRigidArgs {
     int          nf;          // number of free bodies
@@ -71,6 +79,10 @@ struct MgRigidArgs {
     float*       out_root;    // [na][13] actor root tensor
     const int*   out_body;    // [nb] internal slot -> global body (rigid-body row)
     const int*   out_root_row;// [nb] internal slot -> actor row (-1: not a root)
+    // the four arrays above packed per slot, or null: use the separate arrays
+    // (read by the one-round forms of k_rigid_step1 only; callers that pass
+    // free_ids leave it null)
+    const MgSlotRec* slot_rec;// [nb]
     // ground friction patches of the single-shape bodies (persistent, DESIGN.md
     // §3.2.1): SoA [MG_FP_N][gstride], slot b = internal slot b < nf1
     float*       gpatch;

@@ -517,8 +517,9 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
 // (ground_patch_update). The record (MG_FP_N floats, the coupled record's layout) lives in
 // HBM, SoA [MG_FP_N][nf1]: field 0 (the anchor count) is written every step,
 // the rest only while anchors are held; a body that cannot touch the ground at
-// the step's start (the far skip below) does not read it — its first substep
-// has no contact, which drops any patch.
+// the step's start (the far skip below) does not use it — its first substep
+// has no contact, which drops any patch (a wide launch does not read it then; a
+// one-round launch has fetched it with its other inputs and selects zeros).
 struct GPatch {
     int cnt;
     bool dirty;     // anchors / normal differ from the stored record (written back at the step's end)
@@ -749,7 +750,7 @@ template <bool PACK, bool ATTR, class B>
 __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const float* T, V3& x, Q4& q, V3& v,
                                             V3& w, V3& fsum, float invm, V3 invI, Q4 iq, V3 com, bool has_ext,
                                             V3 fext, V3 text, const float* hulls, float* gp, int gstride,
-                                            const float* at) {
+                                            const float (&pr)[MG_FP_N], const float* at) {
     const float lin_damp = T[0], ang_damp = T[1], max_lv = T[2], max_av = T[3], grav_on = T[4];
     // the shape record: wide launches read it from the template record (LDS
     // when staged) in each substep's candidate search — registers are scarcer
@@ -782,7 +783,19 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
     {
         const float clear = G.dn(x) + P.pd;
         const bool far = rho >= 0.0f && clear - rho > P.contact_offset + 1e-3f * (1.0f + fabsf(clear) + rho);
-        if (gp && has_shape && !far) {
+        const bool use = gp && has_shape && !far;
+        if constexpr (PACK) {
+            // a one-round launch loaded the record beside its other inputs
+            // (pr, k_rigid_step1): selected here, not read — the same values
+            // for a body that reads it, the same zeros for one that does not
+            R.cnt = (int)(use ? pr[0] : 0.0f);
+            R.nA = vsel(use, v3(pr[1], pr[2], pr[3]), R.nA);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                R.aA[k] = vsel(use, v3(pr[4 + 6 * k], pr[5 + 6 * k], pr[6 + 6 * k]), R.aA[k]);
+                R.aB[k] = vsel(use, v3(pr[7 + 6 * k], pr[8 + 6 * k], pr[9 + 6 * k]), R.aB[k]);
+            }
+        } else if (use) {
             float r[MG_FP_N];
 #pragma unroll
             for (int k = 0; k < MG_FP_N; ++k) r[k] = gp[(size_t)k * gstride];
@@ -1015,51 +1028,140 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
 #ifndef MG_RIGID1_WIDE_WAVES
 #define MG_RIGID1_WIDE_WAVES 3
 #endif
-template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR>
+template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false>
 __global__ void __launch_bounds__(64, UPZ && WIDE ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
 k_rigid_step1(MgStep P, MgRigidArgs A) {
     extern __shared__ float s_trec[];
     const int i = (WIDE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 64 + threadIdx.x;
     RSTAMP(0);
+    if constexpr (!WIDE) {
+        // the kernel arguments the entry needs, as one batch of scalar loads: left
+        // to the compiler they came in three dependent batches, each in front of
+        // the vector loads it feeds (three scalar-cache trips before the first wait)
+        asm volatile("" ::"s"(A.nf), "s"(A.free_ids), "s"(A.nb), "s"(A.slot_rec), "s"(A.gpatch), "s"(A.gstride),
+                     "s"(A.trec), "s"(A.ntb), "s"(A.ext), "s"(A.root_src), "s"(A.state), "s"(P.h));
+    }
     const bool live = i < A.nf;
     const int b = A.free_ids ? A.free_ids[live ? i : A.nf - 1] : (live ? i : A.nf - 1);
     const int nb = A.nb;
-    // this lane's inputs first, so they are in flight with the template staging;
-    // a fused root-state set (migym_capi.cpp) supplies them from the actor's row
-    // of the user tensor instead (the scatter that would have written them)
-    const float* Si = A.state + b;
-    int si = nb;
-    if (A.root_src) {
-        const int rr = A.root_row[b];
-        if (rr >= 0) {
-            Si = A.root_src + (size_t)rr * MG_STATE_N;
-            si = 1;
-        }
-    }
-    V3 x = v3(Si[0 * si], Si[1 * si], Si[2 * si]);
-    Q4 q = q4(Si[3 * si], Si[4 * si], Si[5 * si], Si[6 * si]);
-    V3 v = v3(Si[7 * si], Si[8 * si], Si[9 * si]);
-    V3 w = v3(Si[10 * si], Si[11 * si], Si[12 * si]);
-    const int tb = A.body_tmpl[b];
-#ifdef MG_RIGID1_PREFETCH_OUT
-    // the fused refresh's row indices, in flight with the state loads (loaded at
-    // the end they were one more memory round trip before the last stores)
-    const bool fout = (A.out_rb || A.out_root) && !WIDE;
-    const int pre_ob = fout && A.out_rb ? A.out_body[b] : -1;
-    const int pre_or = fout && A.out_root ? A.out_root_row[b] : -1;
-#endif
+    V3 x, v, w;
+    Q4 q;
+    int tb;
     V3 fext = v3(0.0f, 0.0f, 0.0f), text = v3(0.0f, 0.0f, 0.0f);
-    if (A.ext) {
-        fext = v3(A.ext[0 * nb + b], A.ext[1 * nb + b], A.ext[2 * nb + b]);
-        text = v3(A.ext[3 * nb + b], A.ext[4 * nb + b], A.ext[5 * nb + b]);
-    }
     const float* T;
-    if constexpr (LDS_T) {
-        for (int k = threadIdx.x; k < A.ntb * MG_TREC_N; k += 64) s_trec[k] = A.trec[k];
-        __syncthreads();
-        T = s_trec + tb * MG_TREC_N;
+    // one-round launches: the fused refresh's rows and the ground-patch record at
+    // the step's start, loaded with the other inputs (below)
+    int pre_ob = -1, pre_or = -1;
+    float pr[MG_FP_N];
+    if constexpr (WIDE) {
+        // this lane's inputs first, so they are in flight with the template staging;
+        // a fused root-state set (migym_capi.cpp) supplies them from the actor's row
+        // of the user tensor instead (the scatter that would have written them)
+        const float* Si = A.state + b;
+        int si = nb;
+        if (A.root_src) {
+            const int rr = A.root_row[b];
+            if (rr >= 0) {
+                Si = A.root_src + (size_t)rr * MG_STATE_N;
+                si = 1;
+            }
+        }
+        x = v3(Si[0 * si], Si[1 * si], Si[2 * si]);
+        q = q4(Si[3 * si], Si[4 * si], Si[5 * si], Si[6 * si]);
+        v = v3(Si[7 * si], Si[8 * si], Si[9 * si]);
+        w = v3(Si[10 * si], Si[11 * si], Si[12 * si]);
+        tb = A.body_tmpl[b];
+        if (A.ext) {
+            fext = v3(A.ext[0 * nb + b], A.ext[1 * nb + b], A.ext[2 * nb + b]);
+            text = v3(A.ext[3 * nb + b], A.ext[4 * nb + b], A.ext[5 * nb + b]);
+        }
+        if constexpr (LDS_T) {
+            for (int k = threadIdx.x; k < A.ntb * MG_TREC_N; k += 64) s_trec[k] = A.trec[k];
+            __syncthreads();
+            T = s_trec + tb * MG_TREC_N;
+        } else {
+            T = A.trec + tb * MG_TREC_N;
+        }
+#pragma unroll
+        for (int k = 0; k < MG_FP_N; ++k) pr[k] = 0.0f;   // unused: a wide launch reads the record when near
     } else {
-        T = A.trec + tb * MG_TREC_N;
+        // A one-round launch's time is one wave's memory round trips and its
+        // instruction stream, so everything whose address
+        // depends on the slot alone is issued here, back to back, before the
+        // first wait: the slot's indices as one 16-byte record, the ground-patch
+        // record (selected, not read, in rigid_body1: a far body never uses what
+        // it fetched), the first two rounds of the template staging, the applied
+        // wrench and, with no fused root set, the SoA state. Only the rows of a
+        // fused root set (52-byte records at the record's root_row) and a
+        // template record read from global memory are a second trip. A dead lane
+        // holds the slot of the launch's last body: every address is a live one.
+        MgSlotRec rec;
+        if constexpr (REC) {
+            rec = A.slot_rec[b];
+        } else {   // no record (callers with free_ids): the separate arrays, the same values
+            rec.root_row = A.root_src ? A.root_row[b] : -1;
+            rec.body_tmpl = A.body_tmpl[b];
+            rec.out_body = A.out_rb ? A.out_body[b] : -1;
+            rec.out_root_row = A.out_root ? A.out_root_row[b] : -1;
+        }
+        if (A.gpatch) {
+#pragma unroll
+            for (int k = 0; k < MG_FP_N; ++k) pr[k] = A.gpatch[(size_t)k * A.gstride + b];
+        } else {
+#pragma unroll
+            for (int k = 0; k < MG_FP_N; ++k) pr[k] = 0.0f;
+        }
+        const int nt = A.ntb * MG_TREC_N, l = threadIdx.x;
+        float t0 = 0.0f, t1 = 0.0f;
+        if constexpr (LDS_T) {   // clamped, not branched: the store below is the conditional one
+            t0 = A.trec[min(l, nt - 1)];
+            t1 = A.trec[min(l + 64, nt - 1)];
+        }
+        if (A.ext) {
+            fext = v3(A.ext[0 * nb + b], A.ext[1 * nb + b], A.ext[2 * nb + b]);
+            text = v3(A.ext[3 * nb + b], A.ext[4 * nb + b], A.ext[5 * nb + b]);
+        }
+        float s[MG_STATE_N];
+        if (!A.root_src) {
+#pragma unroll
+            for (int k = 0; k < MG_STATE_N; ++k) s[k] = A.state[k * nb + b];
+        }
+        // keeps the loads above where they are (as one if-else chain with the
+        // same loads below, they were placed behind the wait for the record)
+        asm volatile("" ::: "memory");
+        // the staged template values go to LDS before the second trip is issued:
+        // they arrive with the record (loads return in order), and the reads of
+        // the template record then overlap the root rows' flight
+        if constexpr (LDS_T) {
+            if (l < nt) s_trec[l] = t0;
+            if (l + 64 < nt) s_trec[l + 64] = t1;
+            for (int k = l + 128; k < nt; k += 64) s_trec[k] = A.trec[k];
+            asm volatile("" ::: "memory");
+        }
+        if (!A.root_src) {
+        } else if (rec.root_row >= 0) {
+            // the actor's row of the user tensor (the scatter that would have
+            // written the SoA state): consecutive floats, loaded four at a time
+            const float* Rr = A.root_src + (size_t)rec.root_row * MG_STATE_N;
+#pragma unroll
+            for (int k = 0; k < MG_STATE_N; ++k) s[k] = Rr[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < MG_STATE_N; ++k) s[k] = A.state[k * nb + b];
+        }
+        x = v3(s[0], s[1], s[2]);
+        q = q4(s[3], s[4], s[5], s[6]);
+        v = v3(s[7], s[8], s[9]);
+        w = v3(s[10], s[11], s[12]);
+        tb = rec.body_tmpl;
+        pre_ob = rec.out_body;
+        pre_or = A.out_root ? rec.out_root_row : -1;
+        if constexpr (LDS_T) {
+            __syncthreads();
+            T = s_trec + tb * MG_TREC_N;
+        } else {
+            T = A.trec + tb * MG_TREC_N;
+        }
     }
     // mass row: the template's own when all its bodies share it (the servo scene:
     // no per-body loads), else the body's SoA row (migym_capi.cpp upload)
@@ -1077,7 +1179,10 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     const V3 com = v3(mr[8], mr[9], mr[10]);
     V3 fsum = v3(0.0f, 0.0f, 0.0f);
     RUSE(x.x); RUSE(q.w); RUSE(w.z); RUSE(invm); RUSE(com.z); RUSE(T[4]);
-    RSTAMP(1);   // state, template record, mass row in registers
+    if constexpr (!WIDE) {
+        RUSE(pre_ob); RUSE(pre_or); RUSE(pr[0]); RUSE(pr[MG_FP_N - 1]);
+    }
+    RSTAMP(1);   // state, template record, mass row (one-round: slot and patch records too) in registers
     // this body's ground-patch record (slot b of the SoA [MG_FP_N][gstride] table)
     // and its LDS copy during the frame
     float* gp = live && A.gpatch ? A.gpatch + b : nullptr;
@@ -1088,14 +1193,14 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     }
     if constexpr (UPZ) {
         rigid_body1<!WIDE, ATTR>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text,
-                                 A.hulls, gp, A.gstride, at);
+                                 A.hulls, gp, A.gstride, pr, at);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
         rigid_body1<!WIDE, ATTR>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text, A.hulls,
-                                 gp, A.gstride, at);
+                                 gp, A.gstride, pr, at);
     }
     // the output addresses are recomputed here (an opaque copy of the slot)
     // rather than kept live in registers across the frame
@@ -1117,13 +1222,10 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
         // paired gather k_gather_rb_root would write from the SoA state)
         if (live) {
             const float o[MG_STATE_N] = {x.x, x.y, x.z, q.x, q.y, q.z, q.w, v.x, v.y, v.z, w.x, w.y, w.z};
-#ifdef MG_RIGID1_PREFETCH_OUT
+            // the rows came with the slot record at entry: no load, and so no
+            // wait, stands between the stores above and these
             const int ob = pre_ob;
             const int rr = pre_or;
-#else
-            const int ob = A.out_rb ? A.out_body[bo] : -1;
-            const int rr = A.out_root ? A.out_root_row[bo] : -1;
-#endif
             if (A.out_rb) {
                 float* R = A.out_rb + (size_t)ob * MG_STATE_N;
 #pragma unroll
@@ -1215,6 +1317,8 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
     A2.out_rb = nullptr;     // so is the fused refresh (MG_FUSE_STEP_OUT)
     A2.out_root = nullptr;
     A2.gpatch = nullptr;     // ground patches: single-shape bodies (multi-shape ones keep per-point rows)
+    A2.slot_rec = nullptr;   // the packed slot record: one-round single-shape launches by slot only
+    if (A.free_ids) A1.slot_rec = nullptr;
     A1.nf = A.nf1;
     A2.nf = A.nf - A.nf1;
     if (A.free_ids) {
@@ -1236,17 +1340,23 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         // issue slots: DESIGN.md §3.2).
         const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
         const size_t lds = (size_t)A.ntb * MG_TREC_N * sizeof(float);
+        // a one-round launch with the packed slot record: the builds that read it
+        // (REC; the others keep the four index arrays in their argument registers)
+        const bool rec = A1.slot_rec != nullptr;
 #define MG_K1(U, L) \
     do { \
         if (wide) MG_LAUNCH((k_rigid_step1<U, L, true, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
+        else if (rec) MG_LAUNCH((k_rigid_step1<U, L, false, false, true>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
         else MG_LAUNCH((k_rigid_step1<U, L, false, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
     } while (0)
         if (A1.attr_idx) {
             // a free body owns an attractor: the attractor-aware builds (template
             // records read from global memory: where they live changes no value)
             if (upz && wide) MG_LAUNCH((k_rigid_step1<true, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+            else if (upz && rec) MG_LAUNCH((k_rigid_step1<true, false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
             else if (upz) MG_LAUNCH((k_rigid_step1<true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
             else if (wide) MG_LAUNCH((k_rigid_step1<false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+            else if (rec) MG_LAUNCH((k_rigid_step1<false, false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
             else MG_LAUNCH((k_rigid_step1<false, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
         } else if (lds <= MG_TREC_LDS_MAX) {
             if (upz) MG_K1(true, true);

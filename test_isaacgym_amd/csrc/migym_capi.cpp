@@ -154,6 +154,7 @@ struct mg_sim {
     bool step_out_ok = false;
     int* d_slot_global = nullptr; // [nb] internal slot -> global body (rigid-body tensor row)
     int* d_slot_actor = nullptr;  // [nb] internal slot -> actor row it is the root of, or -1
+    MgSlotRec* d_slot_rec = nullptr;   // [nb] {d_root_row, d_body_tmpl, d_slot_global, d_slot_actor} of each slot
     int last_set_deferred = 0;    // the last mg_set_* left its source to be read by the next simulate
     int* d_actor_dof = nullptr;   // [na+1]
     float* d_cforce = nullptr;    // [3][nb]
@@ -494,7 +495,7 @@ void shape_obb(const float* sh, const float* hulls, float* o) {
 
 void free_all(mg_sim* s) {
     void* ptrs[] = {s->d_state, s->d_mass, s->d_body_tmpl, s->d_free_global, s->d_perm, s->d_tbf, s->d_trec, s->d_tbi, s->d_shapes, s->d_hulls, s->d_shape_obb,
-                    s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
+                    s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_slot_rec, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
                     s->d_dof_props, s->d_artic, s->d_artic_step, s->d_env, s->d_pairs, s->d_fpatch, s->d_gpatch, s->d_chain_uni, s->d_fp_mask, s->d_env_carry, s->d_env_ctab, s->d_link_f, s->d_link_i, s->d_stage, s->d_stage_idx, s->d_host_out,
                     s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams};
     for (void* p : ptrs)
@@ -1248,6 +1249,9 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         HIP_TRY(dalloc(&s->d_body_actor, (size_t)std::max(nb, 1)));
         HIP_TRY(h2d(s->d_body_actor, body_actor.data(), (size_t)nb * sizeof(int)));
     }
+    // the per-slot indices of the free-body step packed into one record per slot
+    // (the same values as d_root_row, d_body_tmpl, d_slot_global, d_slot_actor)
+    std::vector<MgSlotRec> slot_rec((size_t)std::max(nb, 1), MgSlotRec{-1, 0, 0, -1});
     {
         // fusable root sets: every actor root is a single-shape free body of the
         // free-body kernel (internal slots 0..nf1-1), and that kernel steps all
@@ -1263,6 +1267,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         s->roots_free = ok;
         HIP_TRY(dalloc(&s->d_root_row, (size_t)std::max(nb, 1)));
         HIP_TRY(h2d(s->d_root_row, row.data(), (size_t)nb * sizeof(int)));
+        for (int i = 0; i < nb; ++i) slot_rec[i].root_row = row[i];
     }
     {
         // rows the step kernels write with the refresh fused into them
@@ -1273,6 +1278,13 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         HIP_TRY(h2d(s->d_slot_global, order.data(), (size_t)nb * sizeof(int)));
         HIP_TRY(dalloc(&s->d_slot_actor, (size_t)std::max(nb, 1)));
         HIP_TRY(h2d(s->d_slot_actor, slot_actor.data(), (size_t)nb * sizeof(int)));
+        for (int i = 0; i < nb; ++i) {
+            slot_rec[i].body_tmpl = tmpl_int[i];
+            slot_rec[i].out_body = order[i];
+            slot_rec[i].out_root_row = slot_actor[i];
+        }
+        HIP_TRY(dalloc(&s->d_slot_rec, slot_rec.size()));
+        HIP_TRY(h2d(s->d_slot_rec, slot_rec.data(), (size_t)nb * sizeof(MgSlotRec)));
         // chain groups whose fused-refresh rows are affine in the instance
         for (ArticGroup& g : s->groups) {
             g.out_aff = 0;
@@ -1530,6 +1542,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
         A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
         A.trec = s->d_trec; A.ntb = s->ntb;
+        A.slot_rec = s->d_slot_rec;
         A.gpatch = s->d_gpatch;
         A.gstride = std::max(s->nf1, 1);
         A.ext = s->ext_pending ? s->d_ext : nullptr;
