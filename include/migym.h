@@ -405,6 +405,44 @@ int32_t     mg_enable_dof_forces(mg_sim* sim, const int32_t* actor_on, int32_t n
 int32_t     mg_refresh_dof_force(mg_sim* sim, float* dst, int32_t dst_host, void* stream);
 int32_t     mg_num_dof_force_dofs(mg_sim* sim);
 
+/* ---- force sensors -------------------------------------------------------------
+ * gym.create_asset_force_sensor / acquire_force_sensor_tensor /
+ * refresh_force_sensor_tensor: the joint reaction on an articulation's body, the
+ * mean over the frame. With, per body k of the sensor body's
+ * subtree, N_k the frame's net wrench (m (v+ - v-) / dt, (I+ w+ - I- w-) / dt)
+ * about k's centre of mass, G_k its weight, E_k the wrench applied by
+ * mg_apply_rigid_body_force and C_k its contact wrench, the reading is
+ *   sum_k (F_k, T_k + (c_k+ - o_s) x F_k),  (F_k, T_k) = N_k - G_k - E_k - C_k,
+ * about the sensor origin o_s at the end of the frame: what the parent exerts on
+ * the body through its incoming joint (on a fixed base: what the world exerts).
+ * MG_SENSOR_CONSTRAINT selects the part -sum C_k, MG_SENSOR_FORWARD the rest;
+ * MG_SENSOR_WORLD leaves the result in world axes instead of the sensor's.
+ * A frame that began with a DOF or root state set of the sensor's actor, and the
+ * first frame, read exactly 0.
+ *
+ * mg_set_force_sensors replaces the whole table (host array; n = 0 clears it).
+ * Row k of the tensor is sensor k. Validates body indices and poses
+ * (MG_ERR_ARG); a sensor on a single-body actor (no joint; the free-body and
+ * pile kernels keep no contact moment) makes mg_simulate return
+ * MG_ERR_UNSUPPORTED, naming the sensor and the body, until the table is
+ * replaced. The table decides which kernels a simulate launches (two small
+ * kernels of mg_sensor.hip around the step, and k_env_step's contact-moment
+ * builds for coupled envs), so the call waits for the device and is refused
+ * (MG_ERR_STATE) when the last mg_simulate was captured into a graph.
+ * mg_refresh_force_sensor: [n][6] floats (force xyz, torque xyz) into dst
+ * (device, or host when dst_host): one copy, no launch. */
+#define MG_SENSOR_FORWARD    1   /* enable_forward_dynamics_forces */
+#define MG_SENSOR_CONSTRAINT 2   /* enable_constraint_solver_forces */
+#define MG_SENSOR_WORLD      4   /* use_world_frame */
+typedef struct mg_force_sensor {
+    int32_t body;            /* global rigid-body index */
+    int32_t flags;           /* MG_SENSOR_* */
+    float   p[3], q[4];      /* sensor frame in the body frame */
+} mg_force_sensor;
+int32_t     mg_set_force_sensors(mg_sim* sim, const mg_force_sensor* host, int32_t n);
+int32_t     mg_refresh_force_sensor(mg_sim* sim, float* dst, int32_t dst_host, void* stream);
+int32_t     mg_num_force_sensors(mg_sim* sim);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /

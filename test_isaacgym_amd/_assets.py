@@ -333,6 +333,7 @@ class Asset:
         self.mass_props = []
         self.dof_props = None
         self.shape_props = []
+        self.force_sensors = []   # (body index, local Transform, ForceSensorProperties): create_asset_force_sensor
 
     # ---- derived structure
     @property

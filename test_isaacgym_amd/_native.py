@@ -109,6 +109,15 @@ class MgAttractor(ctypes.Structure):
     ]
 
 
+class MgForceSensor(ctypes.Structure):
+    """mg_force_sensor (include/migym.h): one force sensor."""
+    _fields_ = [
+        ("body", ctypes.c_int32), ("flags", ctypes.c_int32),
+        ("p", ctypes.c_float * 3), ("q", ctypes.c_float * 4),
+    ]
+
+
+MG_SENSOR_FORWARD, MG_SENSOR_CONSTRAINT, MG_SENSOR_WORLD = 1, 2, 4   # include/migym.h
 MG_RENDER_MAX_SHAPES = 64
 
 
@@ -176,6 +185,9 @@ def _load():
         "mg_enable_dof_forces": (i32, [vp, vp, i32]),
         "mg_refresh_dof_force": (i32, [vp, vp, i32, vp]),
         "mg_num_dof_force_dofs": (i32, [vp]),
+        "mg_set_force_sensors": (i32, [vp, vp, i32]),
+        "mg_refresh_force_sensor": (i32, [vp, vp, i32, vp]),
+        "mg_num_force_sensors": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -203,6 +215,7 @@ EXPORTED_SYMBOLS = (
     "mg_debug_copy_env_ctab", "mg_debug_artic_groups", "mg_step_untimed_launches", "mg_cube_pick_step", "mg_env_ctab_floats", "mg_env_carry_floats",
     "mg_set_attractors", "mg_set_attractor_targets", "mg_num_attractors",
     "mg_enable_dof_forces", "mg_refresh_dof_force", "mg_num_dof_force_dofs",
+    "mg_set_force_sensors", "mg_refresh_force_sensor", "mg_num_force_sensors",
 )
 
 

@@ -262,6 +262,10 @@ class Sim:
         # DOF force tensor (Actor.dof_force_on): the per-actor flags are sent
         # after the upload, and at once by a later enable
         self.dof_force_dirty = False
+        # force sensors (Asset.force_sensors): the table is sent
+        # once, by the first simulate or the tensor's acquire, whichever comes
+        # first; from then on no sensor can be added
+        self.force_sensors_frozen = False
 
     @property
     def renderer(self):
@@ -715,6 +719,71 @@ class Sim:
                 pose[k, 0:3], pose[k, 3:7] = tp, tq
             N.check(N.lib.mg_set_attractor_targets(self.native, pose.ctypes.data, lo, hi - lo),
                     "mg_set_attractor_targets")
+
+    # ------------------------------------------------------------ force sensors
+    def force_sensor_rows(self):
+        """(actor, asset sensor) of every force sensor in the tensor's row
+        order: env, then actor, then the asset's sensor order."""
+        return [(a, fs) for a in self.actors for fs in a.asset.force_sensors]
+
+    def force_sensor_first(self, actor):
+        """Row of the actor's first sensor."""
+        n = 0
+        for a in self.actors:
+            if a is actor:
+                return n
+            n += len(a.asset.force_sensors)
+        raise ValueError("actor not in this sim")
+
+    def force_sensor_table(self):
+        """The packed mg_force_sensor table handed to mg_set_force_sensors; the
+        local pose's offset follows the actor's scale. A sensor on a
+        single-body actor is refused here as the library refuses it."""
+        self._assign_indices()
+        rows = self.force_sensor_rows()
+        tab = (N.MgForceSensor * max(len(rows), 1))()
+        for k, (a, (body, pose, props)) in enumerate(rows):
+            if a.num_bodies < 2:
+                raise N.MigymError(
+                    "force sensor %d on rigid body %d: a single-body actor has no joint to measure (and the "
+                    "free-body and pile kernels keep no contact moment); force sensors sit on bodies of "
+                    "articulations" % (k, a.global_body + body))
+            r = tab[k]
+            r.body = a.global_body + body
+            r.flags = ((N.MG_SENSOR_FORWARD if props.enable_forward_dynamics_forces else 0) |
+                       (N.MG_SENSOR_CONSTRAINT if props.enable_constraint_solver_forces else 0) |
+                       (N.MG_SENSOR_WORLD if props.use_world_frame else 0))
+            r.p[:] = [pose.p.x * a.scale, pose.p.y * a.scale, pose.p.z * a.scale]
+            r.q[:] = [pose.r.x, pose.r.y, pose.r.z, pose.r.w]
+        return tab, len(rows)
+
+    def push_force_sensors(self):
+        """Send the table (once) and make the tensor; no sensor is added after."""
+        if self.force_sensors_frozen:
+            return
+        tab, n = self.force_sensor_table()
+        self.finalize()
+        if n and self.native is not None and torch.cuda.is_current_stream_capturing():
+            raise N.MigymError("force sensors: the table is sent by the first simulate or by "
+                               "acquire_force_sensor_tensor, which cannot happen inside a graph capture; "
+                               "acquire the tensor (or step once) before capturing")
+        t = torch.zeros((n, 6), dtype=torch.float32, device=self.device)
+        if self.device.type == "cpu" and n and N.device_count() > 0 and torch.cuda.is_available():
+            t = t.pin_memory()       # filled by a D2H copy at its refresh, as the DOF force tensor
+        self.tensors["force_sensor"] = t
+        self.force_sensors_frozen = True
+        if self.native is not None and n:
+            N.check(N.lib.mg_set_force_sensors(self.native, tab, n), "mg_set_force_sensors")
+
+    def force_sensor_row(self, index):
+        """One row of the tensor as the last simulate left it (numpy, 6)."""
+        self.push_force_sensors()
+        n = self.tensors["force_sensor"].shape[0]
+        out = np.zeros((max(n, 1), 6), dtype=np.float32)
+        if self.native is not None and n:
+            N.check(N.lib.mg_refresh_force_sensor(self.native, out.ctypes.data, 1, self.stream()),
+                    "mg_refresh_force_sensor")
+        return out[index]
 
     def require_native(self, what):
         self.finalize()

@@ -594,6 +594,48 @@ class AttractorProperties(_Params):
         return c
 
 
+class ForceSensorProperties(_Params):
+    """gym.create_asset_force_sensor's properties; the defaults are Isaac
+    Gym's. The forward-dynamics part of a reading is N - G - E, the
+    constraint-solver part -C."""
+
+    def __init__(self):
+        self.enable_forward_dynamics_forces = True
+        self.enable_constraint_solver_forces = True
+        self.use_world_frame = False
+
+    def copy(self):
+        c = ForceSensorProperties()
+        c.__dict__.update(self.__dict__)
+        return c
+
+
+class SpatialForce:
+    """A wrench: force and torque Vec3s."""
+    __slots__ = ("force", "torque")
+
+    def __init__(self, force=None, torque=None):
+        self.force = force if force is not None else Vec3(0.0, 0.0, 0.0)
+        self.torque = torque if torque is not None else Vec3(0.0, 0.0, 0.0)
+
+    def __repr__(self):
+        return "SpatialForce(force=%r, torque=%r)" % (self.force, self.torque)
+
+
+class ForceSensor:
+    """gym.get_actor_force_sensor's handle: get_forces() is the sensor's row
+    of the force sensor tensor as the last simulate left it."""
+    __slots__ = ("_sim", "global_index")
+
+    def __init__(self, sim, global_index):
+        self._sim = sim
+        self.global_index = int(global_index)
+
+    def get_forces(self):
+        r = self._sim.force_sensor_row(self.global_index)
+        return SpatialForce(Vec3(float(r[0]), float(r[1]), float(r[2])), Vec3(float(r[3]), float(r[4]), float(r[5])))
+
+
 class TriangleMeshParams(_Params):
     def __init__(self):
         self.nb_vertices = 0

@@ -1471,7 +1471,9 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
 }
 
 // FRC (here and in k_artic_lanes): the build that reports the DOF force tensor
-template <int MAXL, int G, bool ATTR, bool FRC>
+// SENS: the build that keeps the links' contact moments for the force sensors
+// (MgEnvArgs::ctorque)
+template <int MAXL, int G, bool ATTR, bool FRC, bool SENS = false>
 __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     constexpr int MAXCT = maxct<G>();
@@ -2028,6 +2030,11 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
         // (normal impulses in contact order, then the anchors' friction impulses)
         // (unrolled over the static bounds, so the LDS reads of all rows issue
         // together instead of one dependent round trip per row)
+        // SENS: link ln's contact moment about its COM at this substep's start
+        [[maybe_unused]] V3 tsum = v3(0.0f, 0.0f, 0.0f), lcom = v3(0.0f, 0.0f, 0.0f);
+        if constexpr (SENS) {
+            if (live && blk >= 0) lcom = vadd(S.xl[ln], qrot(S.ql[ln], lk.com));
+        }
         if (live && (ln < L || ln < nfr)) {
 #pragma unroll
             for (int c = 0; c < 2 * MAXCT; ++c) {
@@ -2044,10 +2051,24 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
                         if (fr_) imp = vmad(vscale(S.cd[k][1], S.clam[k][1]), S.cd[k][2], S.clam[k][2]);
                         else imp = vscale(S.cd[k][0], S.clam[k][0]);
                         if (on_link) lsum = vadd(lsum, imp);
+                        if constexpr (SENS) {
+                            if (on_link) tsum = vadd(tsum, vcross(vsub(fr_ ? S.apt[k] : S.cp[k], lcom), imp));
+                        }
                         if (on_fa) fsum = vadd(fsum, imp);
                         if (on_fb) fsum = vsub(fsum, imp);
                     }
                 }
+            }
+        }
+        if constexpr (SENS) {
+            // summed on the output row from launch to launch and divided by dt
+            // in the last one, as FRC's row
+            if (live && blk >= 0) {
+                float* to = A.ctorque + b0 + blk;
+                V3 t = tsum;
+                if (!first) t = vadd(v3(to[0], to[nb], to[2 * (size_t)nb]), t);
+                if (A.last) t = vscale(t, P.inv_dt);
+                to[0] = t.x; to[nb] = t.y; to[2 * (size_t)nb] = t.z;
             }
         }
         if (RB > 0) {
@@ -2371,6 +2392,23 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
 
 }  // namespace
 
+#ifdef MG_ENV_SENS_TU
+// The contact-moment builds of k_env_step (mg_env_sens.hip compiles this file
+// with MG_ENV_SENS_TU set, beside the builds below): a launch with a contact
+// torque row to write. They are the force-reporting builds too (A.dof_frc is
+// always set here), so the sensors add one build per size, not two.
+void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    if (maxl > 16) {
+        if (attr) MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, true, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+        else MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    } else if (maxl > 4) {
+        if (attr) MG_LAUNCH((k_env_step<16, G16, true, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+        else MG_LAUNCH((k_env_step<16, G16, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    } else {
+        MG_LAUNCH((k_env_step<4, G16, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    }
+}
+#else
 // lanes per env / articulation: 16 (4 per wavefront) up to 16 links and 16
 // velocity slots; 64 (one per wavefront) up to MG_MAX_LINKS links and
 // MG_ENV_SLOTS_WIDE slots
@@ -2384,7 +2422,8 @@ static void launch_lanes(int blocks, hipStream_t s, const MgStep& P, const MgArt
 }
 template <int MAXL, int G, bool ATTR>
 static void launch_env_step(int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    if (A.dof_frc) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    if (A.ctorque) mg_launch_env_step_sens(MAXL, ATTR ? 1 : 0, blocks, s, P, A);
+    else if (A.dof_frc) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
     else MG_LAUNCH((k_env_step<MAXL, G, ATTR, false>), dim3(blocks), dim3(64), 0, s, P, A);
 }
 
@@ -2465,3 +2504,4 @@ hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s
 extern "C" int mg_env_carry_floats(void) { return carry_n<64>(); }
 extern "C" int mg_env_ctab_floats(void) { return ct_n<MG_ENV_MAXCT_WIDE>(); }
 int mg_env_ctab_record_floats(int wide) { return wide ? ct_n<MG_ENV_MAXCT_WIDE>() : ct_n<MG_ENV_MAXCT>(); }
+#endif   // MG_ENV_SENS_TU

@@ -228,6 +228,55 @@ struct MgEnvArgs {
     const float* attr;        // [..][MG_ATTR_N]
     // DOF force tensor (MgArticArgs::dof_frc): null unless an actor reports
     float*       dof_frc;
+    // force sensors (mg_sensor.hip): [3][nb] each link's contact
+    // moment about its COM, the frame's mean; set for a group whose articulations
+    // carry a sensor (k_env_step's contact-moment builds, which also write
+    // dof_frc), else null
+    float*       ctorque;
+};
+
+// Force sensors (mg_sensor.hip). Lane = one sensor; the lanes
+// are ordered sensor slot major, articulation instance minor, so neighbouring
+// lanes read neighbouring instances. sens_i rows (SoA, stride n):
+#define MG_SENS_I_G0    0   // global body of the articulation's root (link body j: perm[g0 + j])
+#define MG_SENS_I_LINK0 1   // first row of the template in link_i
+#define MG_SENS_I_LINK  2   // the sensor body's link
+#define MG_SENS_I_MASK  3   // links of its subtree (bit l), virtual links included
+#define MG_SENS_I_FLAGS 4   // MG_SENSOR_* (migym.h)
+#define MG_SENS_I_ART   5   // its articulation among those that carry a sensor
+#define MG_SENS_I_OUT   6   // its row of the tensor (the API's sensor order)
+#define MG_SENS_I_HIST  7   // the articulation's first body in the momentum history
+#define MG_SENS_I_OWNER 8   // 1: this lane keeps the articulation's state copy
+#define MG_SENS_I_N     9
+#define MG_SENS_F_N     7   // sens_f rows: local pose p[3], q[4]
+// sart_i rows ([n_art][MG_SART_I_N]): root body's slot, first DOF, DOFs, first
+// float of its state copy (13 root floats, then pos and vel of each DOF)
+#define MG_SART_I_N     4
+struct MgSensorArgs {
+    int          n;           // sensors
+    int          n_art;       // articulations that carry one
+    int          nb, nd;      // SoA strides of the sim's arrays
+    int          nhb;         // bodies in the momentum history (its stride)
+    const int*   sens_i;      // [MG_SENS_I_N][n]
+    const float* sens_f;      // [MG_SENS_F_N][n]
+    const int*   sart_i;      // [n_art][MG_SART_I_N]
+    const int*   perm;        // [nb] global body -> internal slot
+    const int*   link_i;      // the sim's template link table
+    const float* state;       // [13][nb]
+    const float* mass;        // [12][nb]
+    const int*   body_tmpl;
+    const float* tbf;
+    const float* ext;         // [6][nb]
+    const float* cforce;      // [3][nb]
+    const float* ctorque;     // [3][nb]
+    const float* dof;         // [2][nd]
+    float*       hist;        // [2][6][nhb] end-of-frame momenta, two frames
+    float*       save;        // the articulations' state copies
+    int*         mark;        // [n_art] 1: the frame began with a state set (or is the first)
+    int*         valid;       // [n_art] the state copy and the history hold a frame
+    int*         parity;      // [1] which half of hist the last frame wrote
+    float*       out;         // [n][6]
+    float        g[3], inv_dt;
 };
 
 // Free-body pile step (mg_pile.hip): a coupled env with more
@@ -339,6 +388,10 @@ extern thread_local MgKernelTimer* mg_timer;
 hipError_t mg_launch_render(const MgRenderArgs& A, int nblocks, hipStream_t s);
 hipError_t mg_launch_cube_pick(const mg_cube_pick_args& A, hipStream_t s);
 hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s);
+// k_env_step's contact-moment builds (mg_env_sens.hip): maxl / attr name the build
+void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
+hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s);
 extern "C" int mg_env_carry_floats(void);   // per-env record sizes of the coupled step (mg_env.hip)
 extern "C" int mg_env_ctab_floats(void);

@@ -270,6 +270,30 @@ struct mg_sim {
     std::vector<int> h_actor_dof;         // [na + 1]
     int dof_frc_n = 0;                    // DOFs of the actors that report
 
+    // force sensors (mg_set_force_sensors, mg_sensor.hip). Host
+    // facts kept at upload: every articulation's first global body, first DOF,
+    // template and whether it steps in a coupled env; global body -> its
+    // articulation (-1: a single-body actor); the template tables. The table as
+    // given and its device form (MgSensorArgs), allocated by the first table
+    // with a sensor; sens_tmpl_env: templates whose coupled instances carry a
+    // sensor (their env groups step in k_env_step's contact-moment builds);
+    // sens_err: the refusal mg_simulate reports.
+    struct ArticInfo { int g0, d0, tmpl, coupled; };
+    std::vector<ArticInfo> h_artic_info;
+    std::vector<int> h_body_artic, h_link_i, h_atmpl;
+    std::vector<mg_force_sensor> sensors;
+    std::vector<char> sens_tmpl_env;
+    std::string sens_err;
+    int n_sens = 0, n_sart = 0, sens_nhb = 0;
+    int* d_sens_i = nullptr;
+    float* d_sens_f = nullptr;
+    int* d_sart_i = nullptr;
+    int* d_sens_flag = nullptr;           // mark [n_sart], valid [n_sart], parity [1]
+    float* d_sens_hist = nullptr;
+    float* d_sens_save = nullptr;
+    float* d_sens_out = nullptr;          // [n_sens][6]
+    float* d_ctorque = nullptr;           // [3][nb], allocated with the first sensor table
+
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false;          // mg_set_kernel_timing: events around eager launches
     bool timed_step = false;      // the last simulate recorded ev_begin / ev_end
@@ -497,7 +521,8 @@ void free_all(mg_sim* s) {
     void* ptrs[] = {s->d_state, s->d_mass, s->d_body_tmpl, s->d_free_global, s->d_perm, s->d_tbf, s->d_trec, s->d_tbi, s->d_shapes, s->d_hulls, s->d_shape_obb,
                     s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_slot_rec, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
                     s->d_dof_props, s->d_artic, s->d_artic_step, s->d_env, s->d_pairs, s->d_fpatch, s->d_gpatch, s->d_chain_uni, s->d_fp_mask, s->d_env_carry, s->d_env_ctab, s->d_link_f, s->d_link_i, s->d_stage, s->d_stage_idx, s->d_host_out,
-                    s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams};
+                    s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams,
+                    s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out, s->d_ctorque};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -981,6 +1006,10 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     s->h_body_class.assign(nb, ATTR_NONE);
     s->h_body_grp.assign(nb, -1);
     s->h_body_inst.assign(nb, -1);
+    s->h_body_artic.assign(nb, -1);
+    s->h_artic_info.clear();
+    s->h_link_i.assign(m->tmpl_link_i, m->tmpl_link_i + (size_t)s->ntl * MG_LINK_I_N);
+    s->h_atmpl.assign(m->artic_tmpl_i, m->artic_tmpl_i + (size_t)m->num_artic_tmpls * MG_ATMPL_I_N);
     std::vector<int> artic_sorted, artic_step;
     for (int t = 0; t < m->num_artic_tmpls; ++t) {
         ArticGroup g;
@@ -1031,6 +1060,8 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
                 return fail(MG_ERR_ARG, "articulation %d out of range", k);
             const bool cpl = coupled_body[ai[0]] != 0;
             const bool blk = blocked && !cpl;
+            for (int l = 0; l < g.nbody; ++l) s->h_body_artic[ai[0] + l] = (int)s->h_artic_info.size();
+            s->h_artic_info.push_back({ai[0], ai[1], t, cpl ? 1 : 0});
             if (blk) {
                 blk_k.push_back(k);
                 blk_sorted.push_back((int)artic_sorted.size());
@@ -1380,6 +1411,22 @@ static void fused_targets(mg_sim* s, const float*& tp, const float*& tv, const f
     }
 }
 
+// the force sensor kernels' argument block (mg_sensor.hip)
+static MgSensorArgs sensor_args(const mg_sim* s, const MgStep& P) {
+    MgSensorArgs A{};
+    A.n = s->n_sens; A.n_art = s->n_sart; A.nb = s->nb; A.nd = s->nd; A.nhb = s->sens_nhb;
+    A.sens_i = s->d_sens_i; A.sens_f = s->d_sens_f; A.sart_i = s->d_sart_i;
+    A.perm = s->d_perm; A.link_i = s->d_link_i;
+    A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
+    A.ext = s->d_ext; A.cforce = s->d_cforce; A.ctorque = s->d_ctorque; A.dof = s->d_dof;
+    A.hist = s->d_sens_hist; A.save = s->d_sens_save;
+    A.mark = s->d_sens_flag; A.valid = s->d_sens_flag + s->n_sart; A.parity = s->d_sens_flag + 2 * (size_t)s->n_sart;
+    A.out = s->d_sens_out;
+    for (int k = 0; k < 3; ++k) A.g[k] = P.g[k];
+    A.inv_dt = P.inv_dt;
+    return A;
+}
+
 int32_t mg_simulate(mg_sim* s, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "simulate before the model was uploaded");
     HIP_TRY(hipSetDevice(s->device));
@@ -1408,6 +1455,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // rigid-body attractors: a table this build cannot honour is refused, never
     // ignored; a changed table is sent here, in stream order before the step
     if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
+    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
     if (s->attr_dirty) {
         if (s->capturing) return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
         HIP_TRY(hipMemcpyAsync(s->d_attr, s->h_attr, s->attrs.size() * MG_ATTR_N * sizeof(float),
@@ -1430,6 +1478,12 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // the refresh fused into the step (MG_FUSE_STEP_OUT): every body's rows are
     // written by the kernel that steps it (s->step_out_ok), into the bound
     // tensors (each one optional)
+    if (s->n_sens > 0) {
+        // force sensors: which articulations begin the frame with a state set
+        // (a deferred root set is applied first, so that the comparison sees it)
+        if (int rc_ = flush_root(s, st)) return rc_;
+        HIP_TRY(mg_launch_sensor_mark(sensor_args(s, P), st));
+    }
     const unsigned long long step_cid = capture_id(st);
     const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->step_out_ok &&
                           s->attrs.empty() && (s->bind_root || s->bind_rb || s->bind_dof);
@@ -1522,6 +1576,12 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.attr_idx = s->d_attr_idx;
             A.attr = s->d_attr;
         }
+        if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) {
+            // the contact-moment builds, which are force-reporting builds too
+            // (rows of DOFs that do not report are masked by the refresh)
+            A.ctorque = s->d_ctorque;
+            A.dof_frc = s->d_dof_frc;
+        }
         hipError_t e = mg_launch_env_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
     }
@@ -1588,6 +1648,8 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         if (s->bind_rb) { s->rb_gen = s->state_gen; s->rb_cap = step_cid; }
         if (s->bind_dof) { s->dof_gen = s->dof_sgen; s->dof_cap = step_cid; }
     }
+    // the force sensors' readings, before the applied wrenches are cleared
+    if (s->n_sens > 0) HIP_TRY(mg_launch_force_sensor(sensor_args(s, P), st));
     if (s->ext_pending) {
         HIP_TRY(hipMemsetAsync(s->d_ext, 0, (size_t)s->nb * 6 * sizeof(float), st));
         s->ext_pending = false;
@@ -2085,6 +2147,160 @@ int32_t mg_refresh_dof_force(mg_sim* s, float* dst, int32_t dst_host, void* stre
 }
 
 int32_t mg_num_dof_force_dofs(mg_sim* s) { return s ? s->dof_frc_n : 0; }
+
+// ---- force sensors -------------------------------------------
+int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (n < 0 || (n > 0 && !host)) return fail(MG_ERR_ARG, "bad force sensor table");
+    // the table decides which kernels a simulate launches: a graph captured
+    // before the call would replay the old launches
+    if (s->capturing)
+        return fail(MG_ERR_STATE, "force sensor table changed after the step was captured into a graph (the replays "
+                    "keep the old launches); call it before the capture, or after an eager simulate");
+    HIP_TRY(hipSetDevice(s->device));
+    std::string err;
+    for (int i = 0; i < n; ++i) {
+        const mg_force_sensor& f = host[i];
+        if (f.body < 0 || f.body >= s->nb) return fail(MG_ERR_ARG, "force sensor %d: body %d out of range", i, f.body);
+        bool fin = true;
+        float q2 = 0.0f;
+        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(f.p[k]);
+        for (int k = 0; k < 4; ++k) { fin = fin && std::isfinite(f.q[k]); q2 += f.q[k] * f.q[k]; }
+        if (!fin || !(q2 > 0.0f)) return fail(MG_ERR_ARG, "force sensor %d: the local pose must be finite, its rotation not zero", i);
+        if (s->h_body_artic[f.body] < 0 && err.empty()) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "force sensor %d on rigid body %d: a single-body actor has no joint to measure "
+                     "(and the free-body and pile kernels keep no contact moment); force sensors sit on bodies of "
+                     "articulations", i, f.body);
+            err = buf;
+        }
+    }
+    // lanes: sensor slot (its place among its articulation's sensors) major,
+    // articulation minor, templates apart — neighbouring lanes read
+    // neighbouring instances
+    struct Lane { int tmpl, slot, art, row; };
+    std::vector<Lane> lanes;
+    std::vector<int> art_slot(s->h_artic_info.size(), 0), art_id(s->h_artic_info.size(), -1);
+    std::vector<int> sart, hist0;
+    std::vector<char> tmpl_env(s->h_atmpl.size() / MG_ATMPL_I_N, 0);
+    int nhb = 0, nsave = 0;
+    if (err.empty())
+        for (int i = 0; i < n; ++i) {
+            const int a = s->h_body_artic[host[i].body];
+            const mg_sim::ArticInfo& ai = s->h_artic_info[a];
+            if (art_id[a] < 0) {
+                art_id[a] = (int)hist0.size();
+                const int ndof = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 2];
+                const int nl = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 1], l0 = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 0];
+                int nbody = 0;
+                for (int l = 0; l < nl; ++l) nbody += s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] >= 0 ? 1 : 0;
+                const int row[MG_SART_I_N] = {s->h_perm[ai.g0], ai.d0, ndof, nsave};
+                sart.insert(sart.end(), row, row + MG_SART_I_N);
+                hist0.push_back(nhb);
+                nhb += nbody;
+                nsave += MG_STATE_N + 2 * ndof;
+                if (ai.coupled) tmpl_env[ai.tmpl] = 1;
+            }
+            lanes.push_back({ai.tmpl, art_slot[a]++, art_id[a], i});
+        }
+    std::stable_sort(lanes.begin(), lanes.end(), [](const Lane& x, const Lane& y) {
+        return x.tmpl != y.tmpl ? x.tmpl < y.tmpl : (x.slot != y.slot ? x.slot < y.slot : x.art < y.art);
+    });
+    const int nl_ = (int)lanes.size(), nart = (int)hist0.size();
+    std::vector<int> si((size_t)MG_SENS_I_N * std::max(nl_, 1), 0);
+    std::vector<float> sf((size_t)MG_SENS_F_N * std::max(nl_, 1), 0.0f);
+    for (int t = 0; t < nl_; ++t) {
+        const Lane& L = lanes[t];
+        const mg_force_sensor& f = host[L.row];
+        const mg_sim::ArticInfo& ai = s->h_artic_info[s->h_body_artic[f.body]];
+        const int l0 = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 0], nl = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 1];
+        // the sensor body's link, and its subtree (links in topological order:
+        // a link joins when its parent is in)
+        int ls = -1;
+        for (int l = 0; l < nl; ++l)
+            if (s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] == f.body - ai.g0) ls = l;
+        if (ls < 0) return fail(MG_ERR_ARG, "force sensor %d: body %d is no link of its articulation", L.row, f.body);
+        unsigned mask = 1u << ls;
+        for (int l = ls + 1; l < nl; ++l) {
+            const int p = s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 0];
+            if (p >= 0 && ((mask >> p) & 1u)) mask |= 1u << l;
+        }
+        si[(size_t)MG_SENS_I_G0 * nl_ + t] = ai.g0;
+        si[(size_t)MG_SENS_I_LINK0 * nl_ + t] = l0;
+        si[(size_t)MG_SENS_I_LINK * nl_ + t] = ls;
+        si[(size_t)MG_SENS_I_MASK * nl_ + t] = (int)mask;
+        si[(size_t)MG_SENS_I_FLAGS * nl_ + t] = f.flags & (MG_SENSOR_FORWARD | MG_SENSOR_CONSTRAINT | MG_SENSOR_WORLD);
+        si[(size_t)MG_SENS_I_ART * nl_ + t] = L.art;
+        si[(size_t)MG_SENS_I_OUT * nl_ + t] = L.row;
+        si[(size_t)MG_SENS_I_HIST * nl_ + t] = hist0[L.art];
+        si[(size_t)MG_SENS_I_OWNER * nl_ + t] = L.slot == 0 ? 1 : 0;
+        const float qn = 1.0f / std::sqrt(f.q[0] * f.q[0] + f.q[1] * f.q[1] + f.q[2] * f.q[2] + f.q[3] * f.q[3]);
+        for (int k = 0; k < 3; ++k) sf[(size_t)k * nl_ + t] = f.p[k];
+        for (int k = 0; k < 4; ++k) sf[(size_t)(3 + k) * nl_ + t] = f.q[k] * qn;
+    }
+    // fresh device buffers, committed at the end: an error leaves the table as it was
+    HIP_TRY(hipDeviceSynchronize());
+    int *d_i = nullptr, *d_sart = nullptr, *d_flag = nullptr;
+    float *d_f = nullptr, *d_hist = nullptr, *d_save = nullptr, *d_out = nullptr;
+    auto drop = [&]() {
+        void* ps[] = {d_i, d_sart, d_flag, d_f, d_hist, d_save, d_out};
+        for (void* p : ps)
+            if (p) (void)hipFree(p);
+    };
+    if (nl_ > 0) {
+        hipError_t e = dalloc(&d_i, si.size());
+        if (e == hipSuccess) e = dalloc(&d_f, sf.size());
+        if (e == hipSuccess) e = dalloc(&d_sart, sart.size());
+        if (e == hipSuccess) e = dalloc(&d_flag, (size_t)2 * nart + 1);
+        if (e == hipSuccess) e = dalloc(&d_hist, (size_t)12 * nhb);
+        if (e == hipSuccess) e = dalloc(&d_save, (size_t)nsave);
+        if (e == hipSuccess) e = dalloc(&d_out, (size_t)6 * nl_);
+        if (e == hipSuccess && !s->d_ctorque) {
+            e = dalloc(&s->d_ctorque, (size_t)3 * std::max(s->nb, 1));
+            if (e == hipSuccess) e = hipMemset(s->d_ctorque, 0, (size_t)3 * std::max(s->nb, 1) * sizeof(float));
+        }
+        if (e == hipSuccess) e = hipMemcpy(d_i, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_f, sf.data(), sf.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_sart, sart.data(), sart.size() * sizeof(int), hipMemcpyHostToDevice);
+        // no frame held yet: every articulation's first frame reads 0
+        if (e == hipSuccess) e = hipMemset(d_flag, 0, ((size_t)2 * nart + 1) * sizeof(int));
+        if (e == hipSuccess) e = hipMemset(d_hist, 0, (size_t)12 * std::max(nhb, 1) * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(d_save, 0, (size_t)std::max(nsave, 1) * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(d_out, 0, (size_t)6 * nl_ * sizeof(float));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            drop();
+            return fail(MG_ERR_DEVICE, "force sensor table: %s", hipGetErrorString(e));
+        }
+    }
+    void* old[] = {s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out};
+    for (void* p : old)
+        if (p) (void)hipFree(p);
+    s->d_sens_i = d_i; s->d_sens_f = d_f; s->d_sart_i = d_sart; s->d_sens_flag = d_flag;
+    s->d_sens_hist = d_hist; s->d_sens_save = d_save; s->d_sens_out = d_out;
+    s->sensors.assign(host, host + n);
+    s->n_sens = nl_;
+    s->n_sart = nart;
+    s->sens_nhb = nhb;
+    s->sens_tmpl_env = tmpl_env;
+    s->sens_err = err;
+    return MG_OK;
+}
+
+int32_t mg_refresh_force_sensor(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
+    if (s->n_sens == 0) return MG_OK;
+    if (!dst) return fail(MG_ERR_ARG, "null destination");
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)s->n_sens * 6 * sizeof(float);
+    HIP_TRY(hipMemcpyAsync(dst, s->d_sens_out, bytes, dst_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (dst_host) HIP_TRY(hipStreamSynchronize(st));
+    return MG_OK;
+}
+
+int32_t mg_num_force_sensors(mg_sim* s) { return s ? (int32_t)s->sensors.size() : 0; }
 
 int32_t mg_refresh_net_contact_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");

@@ -152,6 +152,8 @@ class Gym:
 
     def simulate(self, sim):
         """One frame (test10_servo_vecenv.py:380): the fused HIP step kernels."""
+        if not sim.force_sensors_frozen:
+            sim.push_force_sensors()       # refuses a sensor on a single-body actor
         h = sim.require_native("gym.simulate")
         _check_held(sim, "simulate")
         sim.push_attractors()
@@ -1087,6 +1089,61 @@ class Gym:
         N.check(N.lib.mg_refresh_dof_force(sim.native, full.ctypes.data, 1, sim.stream()), "mg_refresh_dof_force")
         out[:] = full[a.global_dof:a.global_dof + a.num_dofs]
         return out
+
+    # ---- force sensors (include/migym.h)
+    def create_asset_force_sensor(self, asset, body_idx, local_pose, props=None):
+        """A force sensor on body `body_idx` of every actor made from the
+        asset, at `local_pose` in the body frame: the joint reaction the body's
+        parent exerts on it (on a fixed base: the world). Returns the asset's
+        sensor index, or -1. Before prepare_sim or the first simulate, and
+        before the tensor is acquired."""
+        if asset is None or not 0 <= int(body_idx) < len(asset.bodies):
+            print("*** migym: create_asset_force_sensor: invalid rigid body index %r" % (body_idx,), file=sys.stderr)
+            return _T.INVALID_HANDLE
+        for sim in self._sims:
+            if any(x is asset for x in sim.assets) and sim.force_sensors_frozen:
+                print("*** migym: create_asset_force_sensor: the sim has stepped or handed out its force sensor "
+                      "tensor; create force sensors before the first simulate and before "
+                      "acquire_force_sensor_tensor", file=sys.stderr)
+                return _T.INVALID_HANDLE
+        pose = _T._as_transform(local_pose) if local_pose is not None else Transform()
+        p = props.copy() if props is not None else _T.ForceSensorProperties()
+        asset.force_sensors.append((int(body_idx), pose, p))
+        return len(asset.force_sensors) - 1
+
+    def get_asset_force_sensor_count(self, asset):
+        return len(asset.force_sensors)
+
+    def get_actor_force_sensor_count(self, env, handle):
+        return len(self._actor(env, handle).asset.force_sensors)
+
+    def get_actor_force_sensor(self, env, handle, index):
+        """The actor's index-th sensor (the asset's order): a handle whose
+        get_forces() returns the last frame's SpatialForce."""
+        a = self._actor(env, handle)
+        if not 0 <= index < len(a.asset.force_sensors):
+            return None
+        return _T.ForceSensor(env.sim, env.sim.force_sensor_first(a) + index)
+
+    def get_sim_force_sensor_count(self, sim):
+        return len(sim.force_sensor_rows())
+
+    def acquire_force_sensor_tensor(self, sim):
+        """(num_sensors, 6) float32: force xyz, then torque xyz; rows by env,
+        then actor, then the asset's sensor order; the same storage on every
+        call."""
+        sim.push_force_sensors()
+        return Tensor(sim.tensors["force_sensor"])
+
+    def refresh_force_sensor_tensor(self, sim):
+        sim.push_force_sensors()
+        t = sim.tensors["force_sensor"]
+        if t.numel() == 0:
+            return True
+        h = sim.require_native("refresh_force_sensor_tensor")
+        N.check(N.lib.mg_refresh_force_sensor(h, t.data_ptr(), 1 if t.device.type == "cpu" else 0, sim.stream()),
+                "refresh_force_sensor_tensor")
+        return True
 
     def _set(self, sim, tensor, fn, ncols, nrows, what, index=None, count=None):
         sim.finalize()
