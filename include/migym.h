@@ -443,6 +443,56 @@ int32_t     mg_set_force_sensors(mg_sim* sim, const mg_force_sensor* host, int32
 int32_t     mg_refresh_force_sensor(mg_sim* sim, float* dst, int32_t dst_host, void* stream);
 int32_t     mg_num_force_sensors(mg_sim* sim);
 
+/* ---- rigid contact list -----------------------------------------------------
+ * Which bodies touch, where and how hard (gym.get_rigid_contacts; DESIGN.md
+ * §3.14): one record per contact point and per friction anchor of the frame's
+ * last substep, in a device-resident list. While reporting is on, mg_simulate
+ * launches the reporting builds of the step kernels, which keep what they
+ * otherwise only sum into the net contact force, and one compaction
+ * (mg_contact.hip) that packs the records in a fixed order: free bodies of
+ * uncoupled envs by storage slot (single-shape bodies first, each group in
+ * body order), then coupled envs, then pile envs by env index, each owner's
+ * entries in its kernel's own contact order, an owner's anchors after its
+ * points. The listed impulses of a body sum to its row of the net contact
+ * force times dt (substeps = 1; with more substeps the list is the last
+ * substep's, the tensor the frame's).
+ *
+ * body0 / body1 are global rigid-body indices, -1 the ground plane. kind 0 is a
+ * contact point (lambda: its normal impulse in N s along n, the direction it
+ * pushes body0), kind 1 a friction anchor (lambda 0, fimp: its friction impulse
+ * on body0, a world vector). A multi-shape free body and the bodies of a pile
+ * env have per-point friction rows instead of anchors: their points carry fimp
+ * themselves. In a coupled env friction acts on the pairs' anchors: its points
+ * come first (the contact table's order), then its anchors; a point's mu is
+ * its pair's anchors' (0 when the pair holds none); joint-limit rows are not
+ * listed. A free body lists at most 8 entries, a coupled env 16 + 16 (48 + 48
+ * in a 64-lane env), a pile env 256. separation is the
+ * value the solver rows start the substep with (less the rest offset); p is a
+ * world point.
+ *
+ * mg_set_contact_reporting: on != 0 turns reporting on with room for
+ * `capacity` records (0: the worst case of the model); records past the
+ * capacity are dropped, never written. It decides which kernels a simulate
+ * launches, so the call waits for the device and is refused (MG_ERR_STATE) when
+ * the last mg_simulate was captured into a graph, whose replays would keep the
+ * old launches: call it before the capture, or after an eager mg_simulate.
+ * While reporting is on mg_step_out_supported is 0, and the coupled envs step
+ * in force-reporting builds (the DOF force tensor's rows of actors that do not
+ * report stay masked).
+ * mg_refresh_rigid_contacts: copies min(stored, cap) records into dst (device,
+ * or host when dst_host), returns their number (< 0 on error) and sets *total
+ * (may be NULL) to the true number of the last simulate, so a caller sees a
+ * drop. Before the first reporting simulate it returns 0. It waits for
+ * `stream`, then makes one copy and no launch. */
+typedef struct mg_rigid_contact {   /* 64 bytes */
+    int32_t env, body0, body1, kind;
+    float   p[3], n[3], separation, lambda, fimp[3], mu;
+} mg_rigid_contact;
+int32_t     mg_set_contact_reporting(mg_sim* sim, int32_t on, int32_t capacity);
+int32_t     mg_contact_reporting(mg_sim* sim);              /* 0 / 1 */
+int32_t     mg_refresh_rigid_contacts(mg_sim* sim, mg_rigid_contact* dst, int32_t cap, int32_t dst_host,
+                                      int32_t* total, void* stream);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /

@@ -8,6 +8,8 @@ raises, and on a host without a GPU ``mg_create_sim`` fails and
 import ctypes
 import os
 
+import numpy as np
+
 import torch  # noqa: F401  -- load torch's HIP runtime first, so libmigym binds to the same one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +120,24 @@ class MgForceSensor(ctypes.Structure):
 
 
 MG_SENSOR_FORWARD, MG_SENSOR_CONSTRAINT, MG_SENSOR_WORLD = 1, 2, 4   # include/migym.h
+
+
+class MgRigidContact(ctypes.Structure):
+    """mg_rigid_contact (include/migym.h): one record of the rigid contact list."""
+    _fields_ = [
+        ("env", ctypes.c_int32), ("body0", ctypes.c_int32), ("body1", ctypes.c_int32), ("kind", ctypes.c_int32),
+        ("p", ctypes.c_float * 3), ("n", ctypes.c_float * 3),
+        ("separation", ctypes.c_float), ("lambda_", ctypes.c_float),
+        ("fimp", ctypes.c_float * 3), ("mu", ctypes.c_float),
+    ]
+
+
+# the same record as a numpy dtype (64 bytes)
+RIGID_CONTACT_DTYPE = np.dtype([
+    ("env", "<i4"), ("body0", "<i4"), ("body1", "<i4"), ("kind", "<i4"),
+    ("p", "<f4", (3,)), ("n", "<f4", (3,)), ("separation", "<f4"), ("lambda", "<f4"),
+    ("fimp", "<f4", (3,)), ("mu", "<f4"),
+])
 MG_RENDER_MAX_SHAPES = 64
 
 
@@ -188,6 +208,9 @@ def _load():
         "mg_set_force_sensors": (i32, [vp, vp, i32]),
         "mg_refresh_force_sensor": (i32, [vp, vp, i32, vp]),
         "mg_num_force_sensors": (i32, [vp]),
+        "mg_set_contact_reporting": (i32, [vp, i32, i32]),
+        "mg_contact_reporting": (i32, [vp]),
+        "mg_refresh_rigid_contacts": (i32, [vp, vp, i32, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -216,6 +239,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_attractors", "mg_set_attractor_targets", "mg_num_attractors",
     "mg_enable_dof_forces", "mg_refresh_dof_force", "mg_num_dof_force_dofs",
     "mg_set_force_sensors", "mg_refresh_force_sensor", "mg_num_force_sensors",
+    "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
 )
 
 

@@ -266,6 +266,13 @@ class Sim:
         # once, by the first simulate or the tensor's acquire, whichever comes
         # first; from then on no sensor can be added
         self.force_sensors_frozen = False
+        # rigid contact list: the switch (on, max_contacts) as
+        # asked for, sent after the upload and at once by a later call;
+        # contact_first_query: the stderr note of the first get_*_rigid_contacts
+        # that turned reporting on itself was printed
+        self.contact_reporting = (False, 0)
+        self.contact_reporting_dirty = False
+        self.contact_first_query = False
 
     @property
     def renderer(self):
@@ -639,6 +646,7 @@ class Sim:
         self.tensors["dof_force"] = frc
         self.finalized = True
         self.push_dof_force_flags()
+        self.push_contact_reporting()
 
     def push_dof_force_flags(self):
         """Send the per-actor reporting flags (mg_enable_dof_forces) if they
@@ -648,6 +656,49 @@ class Sim:
         on = np.array([1 if a.dof_force_on else 0 for a in self.actors], dtype=np.int32)
         self.dof_force_dirty = False
         N.check(N.lib.mg_enable_dof_forces(self.native, on.ctypes.data, len(on)), "mg_enable_dof_forces")
+
+    def set_contact_reporting(self, on, max_contacts=0):
+        """gym.set_rigid_contact_reporting: the switch is kept here and sent
+        (mg_set_contact_reporting) once the model is uploaded."""
+        want = (bool(on), max(int(max_contacts), 0))
+        if want != self.contact_reporting:
+            prev = self.contact_reporting
+            self.contact_reporting = want
+            self.contact_reporting_dirty = True
+            if self.finalized:
+                try:
+                    self.push_contact_reporting()
+                except N.MigymError:
+                    self.contact_reporting = prev
+                    raise
+
+    def push_contact_reporting(self):
+        if self.native is None or not self.contact_reporting_dirty:
+            return
+        on, cap = self.contact_reporting
+        self.contact_reporting_dirty = False
+        N.check(N.lib.mg_set_contact_reporting(self.native, 1 if on else 0, cap), "mg_set_contact_reporting")
+
+    def rigid_contact_records(self):
+        """The contact list of the last simulate as a host array of
+        _native.RIGID_CONTACT_DTYPE records (mg_refresh_rigid_contacts), and the
+        true number of entries that simulate found (more than the array's length
+        when max_contacts dropped some)."""
+        empty = np.zeros(0, dtype=N.RIGID_CONTACT_DTYPE)
+        if self.native is None or not self.contact_reporting[0]:
+            return empty, 0
+        total = ctypes.c_int32(0)
+        cap = max(self.contact_reporting[1], 1024)
+        for _ in range(2):
+            buf = np.zeros(cap, dtype=N.RIGID_CONTACT_DTYPE)
+            n = N.lib.mg_refresh_rigid_contacts(self.native, buf.ctypes.data, cap, 1, ctypes.byref(total),
+                                                self.stream())
+            if n < 0:
+                N.check(n, "mg_refresh_rigid_contacts")
+            if n < cap or total.value <= cap:
+                break
+            cap = total.value     # our buffer was the limit, not the sim's capacity: once more
+        return buf[:n].copy(), int(total.value)
 
     def _push_dof_targets_all(self):
         if self.num_dofs == 0:

@@ -348,6 +348,24 @@ class RigidBodyState:
     dtype = np.dtype([("pose", Transform.dtype), ("vel", Velocity.dtype)])
 
 
+class RigidContact:
+    """gym.get_env_rigid_contacts / get_rigid_contacts records (DESIGN.md §3.14,
+    §6): Isaac Gym's field names. body0 / body1 are env-local rigid-body indices
+    (-1: the ground), localPos* the contact point in each body's frame (the env
+    point for the ground and static bodies), normal the direction a positive
+    lambda pushes body0, minDist the separation, lambda the normal impulse,
+    lambdaFriction the friction impulse on (t1, t2), friction the coefficient;
+    the other fields are not modelled and read 0."""
+    dtype = np.dtype([
+        ("env0", "<i4"), ("env1", "<i4"), ("body0", "<i4"), ("body1", "<i4"),
+        ("localPos0", Vec3.dtype), ("localPos1", Vec3.dtype),
+        ("minDist", "<f4"), ("initialOverlap", "<f4"), ("normal", Vec3.dtype),
+        ("offset0", Vec3.dtype), ("offset1", Vec3.dtype),
+        ("lambda", "<f4"), ("lambdaFriction", [("x", "<f4"), ("y", "<f4")]),
+        ("friction", "<f4"), ("torsionFriction", "<f4"), ("rollingFriction", "<f4"),
+    ])
+
+
 class DofState:
     dtype = np.dtype([("pos", "<f4"), ("vel", "<f4")])
 

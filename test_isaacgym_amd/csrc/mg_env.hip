@@ -32,6 +32,7 @@
 #include "mg_pairs.h"
 #include "mg_world.h"
 #include "mg_attractor.h"
+#include "mg_contact.h"
 
 #ifdef MG_ENV_PHASE_TIMING
 // profiling build only: per-phase shader-clock cycles summed over waves
@@ -1473,7 +1474,11 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
 // FRC (here and in k_artic_lanes): the build that reports the DOF force tensor
 // SENS: the build that keeps the links' contact moments for the force sensors
 // (MgEnvArgs::ctorque)
-template <int MAXL, int G, bool ATTR, bool FRC, bool SENS = false>
+// CREP: the reporting builds (the rigid contact list, DESIGN.md §3.14;
+// mg_env_crep.hip), launched while contact reporting is on: the frame's last
+// substep leaves the env's contacts and anchors, with their final impulses, in
+// its staging record. They are force-reporting builds too, as the SENS ones.
+template <int MAXL, int G, bool ATTR, bool FRC, bool SENS = false, bool CREP = false>
 __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     constexpr int MAXCT = maxct<G>();
@@ -1726,6 +1731,9 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
                 S.alast[q] = fbits(r[13]);
             }
         }
+        // CREP: the contacts of the table (the joint-limit rows appended below
+        // are no contacts)
+        [[maybe_unused]] const int crep_nc = base < MAXCT ? base : MAXCT;
         __syncthreads();
         // joint-limit rows (PhysX solves limits as constraints): a DOF whose
         // predicted position q + h u lies within 5% of its range of a limit gets
@@ -2058,6 +2066,38 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
                         if (on_fb) fsum = vsub(fsum, imp);
                     }
                 }
+            }
+        }
+        if constexpr (CREP) {
+            // the contact list's staging record: the env's lanes store contact
+            // ln, ln + G, ... then the anchors likewise, from the LDS words the
+            // sums above read. A point's mu is that of its pair's anchors (the
+            // friction rows act there), 0 when the pair holds none.
+            if (A.last && live) {
+                auto gbody = [&](int p) -> int {
+                    if (p < 0) return -1;
+                    const int slot = p >= ST0 ? ei[8 + p - ST0]
+                                              : (p >= F0 ? ei[3 + p - F0] : b0 + A.link_i[p * MG_LINK_I_N + 3]);
+                    return A.crep_body[slot];
+                };
+                float* cr = A.crep + e;
+                const V3 z3 = v3(0.0f, 0.0f, 0.0f);
+                for (int k = ln; k < crep_nc; k += G) {
+                    const int a = S.ca[k], b = S.cb[k];
+                    const int ab = (a & 0xFFFF) | (b << 16);
+                    float mu = 0.0f;
+                    for (int q = 0; q < nanc; ++q)
+                        if (S.aab[q] == ab) mu = S.amu[q];
+                    crep_store(cr, A.crep_stride, k, gbody(a), gbody(b), 0, S.cp[k], S.cd[k][0], S.cs0[k],
+                               S.clam[k][0], z3, mu);
+                }
+                for (int k = ln; k < nanc; k += G) {
+                    const int ab = S.aab[k];
+                    crep_store(cr, A.crep_stride, crep_nc + k, gbody(ab & 0xFFFF), gbody(ab >> 16), 1, S.apt[k],
+                               vcross(S.cd[k][1], S.cd[k][2]), 0.0f, 0.0f,
+                               vmad(vscale(S.cd[k][1], S.clam[k][1]), S.cd[k][2], S.clam[k][2]), S.amu[k]);
+                }
+                if (ln == 0) A.crep_n[e] = crep_nc + nanc;
             }
         }
         if constexpr (SENS) {
@@ -2408,6 +2448,27 @@ void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, cons
         MG_LAUNCH((k_env_step<4, G16, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
     }
 }
+#elif defined(MG_ENV_CREP_TU)
+// The reporting builds of k_env_step (mg_env_crep.hip compiles this file with
+// MG_ENV_CREP_TU set): a launch with a staging record to write, with (sens) or
+// without a contact torque row. A.dof_frc is always set here.
+template <int MAXL, int G, bool ATTR>
+static void launch_crep(int sens, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    if (sens) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true, true, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    else MG_LAUNCH((k_env_step<MAXL, G, ATTR, true, false, true>), dim3(blocks), dim3(64), 0, s, P, A);
+}
+void mg_launch_env_step_crep(int maxl, int attr, int sens, int blocks, hipStream_t s, const MgStep& P,
+                             const MgEnvArgs& A) {
+    if (maxl > 16) {
+        if (attr) launch_crep<MG_MAX_LINKS, 64, true>(sens, blocks, s, P, A);
+        else launch_crep<MG_MAX_LINKS, 64, false>(sens, blocks, s, P, A);
+    } else if (maxl > 4) {
+        if (attr) launch_crep<16, G16, true>(sens, blocks, s, P, A);
+        else launch_crep<16, G16, false>(sens, blocks, s, P, A);
+    } else {
+        launch_crep<4, G16, false>(sens, blocks, s, P, A);
+    }
+}
 #else
 // lanes per env / articulation: 16 (4 per wavefront) up to 16 links and 16
 // velocity slots; 64 (one per wavefront) up to MG_MAX_LINKS links and
@@ -2422,7 +2483,8 @@ static void launch_lanes(int blocks, hipStream_t s, const MgStep& P, const MgArt
 }
 template <int MAXL, int G, bool ATTR>
 static void launch_env_step(int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    if (A.ctorque) mg_launch_env_step_sens(MAXL, ATTR ? 1 : 0, blocks, s, P, A);
+    if (A.crep) mg_launch_env_step_crep(MAXL, ATTR ? 1 : 0, A.ctorque ? 1 : 0, blocks, s, P, A);
+    else if (A.ctorque) mg_launch_env_step_sens(MAXL, ATTR ? 1 : 0, blocks, s, P, A);
     else if (A.dof_frc) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
     else MG_LAUNCH((k_env_step<MAXL, G, ATTR, false>), dim3(blocks), dim3(64), 0, s, P, A);
 }

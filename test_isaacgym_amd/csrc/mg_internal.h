@@ -91,7 +91,47 @@ struct MgRigidArgs {
     // the launch owns one (then the attractor-aware builds step it)
     const int*   attr_idx;    // [nb] internal slot -> record of `attr`, -1: none
     const float* attr;        // [..][MG_ATTR_N]
+    // rigid contact list (mg_contact.h): the staging records of
+    // the free bodies, SoA [MG_CREP_FREE_CAP][MG_CREP_N][crep_stride], slot b at
+    // index b, their entry counts and internal slot -> global body; all null
+    // unless contact reporting is on (then the reporting builds step)
+    float*       crep;
+    int*         crep_n;      // [nf]
+    const int*   crep_body;   // [nb]
+    int          crep_stride;
 };
+
+// Rigid contact list (mg_contact.hip). A reporting build of a
+// step kernel leaves, in the frame's last substep, one fixed-capacity staging
+// record per owner (a free body, a coupled env, a pile env) and its entry
+// count; k_contact_compact packs the records into one list in owner order. A
+// staged entry is MG_CREP_N dwords (mg_contact.h: crep_store); entry k, dword f
+// of owner i lives at stage[(k * MG_CREP_N + f) * stride + i], so the owner
+// index stays the coalesced axis.
+#define MG_CREP_N        16
+#define MG_CREP_FREE_CAP 8    // a free body: 4 points + 2 anchors (one shape), 8 points (several)
+#define MG_CREP_FAMILIES 3    // owner order: free bodies, coupled envs, pile envs
+struct MgContactFamily {
+    int          n;           // owners
+    int          cap;         // entries per staging record
+    int          stride;      // SoA stride of `stage`
+    const float* stage;
+    const int*   count;       // [n]
+    const int*   env;         // [n] owner -> env index
+    const int*   col;         // [n] owner -> its index in stage / count, or null: the owner's own
+};
+struct MgContactArgs {
+    MgContactFamily fam[MG_CREP_FAMILIES];
+    int          n_own;       // owners of all families
+    int          nblk;        // blocks of MG_CREP_BLOCK owners
+    int*         blk_sum;     // [nblk] entries of each block's owners (pass 1 -> pass 2)
+    mg_rigid_contact* out;    // [capacity]
+    int          capacity;
+    int*         header;      // [2] true total, stored total (device)
+    int*         header_host; // the same two ints in mapped host memory (mg_refresh_rigid_contacts)
+};
+#define MG_CREP_BLOCK 256
+hipError_t mg_launch_contact_compact(const MgContactArgs& A, hipStream_t s);
 
 // Articulation step arguments (lane = articulation instance).
 struct MgArticArgs {
@@ -233,6 +273,15 @@ struct MgEnvArgs {
     // carry a sensor (k_env_step's contact-moment builds, which also write
     // dof_frc), else null
     float*       ctorque;
+    // rigid contact list (mg_contact.h): the coupled envs'
+    // staging records, SoA [2 MG_ENV_MAXCT_WIDE][MG_CREP_N][crep_stride], env e
+    // of the launch at index e, their entry counts and internal slot -> global
+    // body; null unless contact reporting is on (k_env_step's reporting builds,
+    // which also write dof_frc)
+    float*       crep;
+    int*         crep_n;      // [ne]
+    const int*   crep_body;   // [nb]
+    int          crep_stride;
 };
 
 // Force sensors (mg_sensor.hip). Lane = one sensor; the lanes
@@ -315,6 +364,13 @@ struct MgPileArgs {
     const float* shape_obb;   // [num_shapes][MG_OBB_N] (pair screen)
     const float* ext;         // [6][nb] or null
     float*       cforce;      // [3][nb]
+    // rigid contact list (mg_contact.h): the pile envs' staging
+    // records, SoA [MG_PILE_MAXPT][MG_CREP_N][ne], their entry counts and
+    // internal slot -> global body; null unless contact reporting is on (then
+    // the reporting build steps)
+    float*       crep;
+    int*         crep_n;      // [ne]
+    const int*   crep_body;   // [nb]
 };
 
 // Camera render (mg_render.hip). One device record per camera; a camera's
@@ -390,6 +446,9 @@ hipError_t mg_launch_cube_pick(const mg_cube_pick_args& A, hipStream_t s);
 hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s);
 // k_env_step's contact-moment builds (mg_env_sens.hip): maxl / attr name the build
 void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+// k_env_step's reporting builds (mg_env_crep.hip): sens: with the contact moment
+void mg_launch_env_step_crep(int maxl, int attr, int sens, int blocks, hipStream_t s, const MgStep& P,
+                             const MgEnvArgs& A);
 hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s);

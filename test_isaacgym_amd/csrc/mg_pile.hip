@@ -28,6 +28,7 @@
 #include "mg_internal.h"
 #include "mg_collide.h"
 #include "mg_pairs.h"
+#include "mg_contact.h"
 
 #ifdef MG_PILE_STAMPS
 // diagnostic build only (tools/kbench_pile_stamps.py): s_memtime stamps of each
@@ -280,6 +281,10 @@ __device__ __forceinline__ void pair_constants(PileLds& S, const PairHdr& H) {
     }
 }
 
+// CREP: the reporting build, launched while contact reporting
+// is on: the last substep's points go to the env's staging record, point order
+// (pair order, then the pair's own), with the impulses the force pass sums.
+template <bool CREP>
 __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
     __shared__ PileLds S;
     const int ln = threadIdx.x;
@@ -613,6 +618,29 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
             __syncthreads();
         }
         if (act) fsum = S.facc[ln];
+        if constexpr (CREP) {
+            if (sub == P.substeps - 1) {
+                // each pair lane its pair's points: entry = point index; per-point
+                // friction rows, so a point carries its friction impulse
+                float* cr = A.crep + blockIdx.x;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const PairHdr& Hu = H[u];
+                    if (ln + 64 * u < nap) {
+                        const int b = Hu.b;
+                        const int g0 = A.crep_body[A.pile_body[boff + Hu.a]];
+                        const int g1 = b < 0 ? -1 : A.crep_body[b < ST0 ? A.pile_body[boff + b] : ei[5 + b - ST0]];
+                        const V3 xca = S.xc[Hu.a];
+                        for (int k = 0; k < Hu.np; ++k) {
+                            const int c = Hu.p0 + k;
+                            crep_store(cr, A.ne, c, g0, g1, 0, vadd(xca, S.ra[c]), S.n[c], S.s0[c], S.ln[c],
+                                       vadd(vscale(S.t1[c], S.lt1[c]), vscale(S.t2[c], S.lt2[c])), Hu.mu);
+                        }
+                    }
+                }
+                if (ln == 0) A.crep_n[blockIdx.x] = npt;
+            }
+        }
         __syncthreads();
         PSTAMP(9);
         PCOUNT(12, npair);
@@ -640,6 +668,7 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
 
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s) {
     if (A.ne <= 0) return hipSuccess;
-    MG_LAUNCH(k_pile_step, dim3(A.ne), dim3(64), 0, s, P, A);
+    if (A.crep) MG_LAUNCH(k_pile_step<true>, dim3(A.ne), dim3(64), 0, s, P, A);
+    else MG_LAUNCH(k_pile_step<false>, dim3(A.ne), dim3(64), 0, s, P, A);
     return hipGetLastError();
 }

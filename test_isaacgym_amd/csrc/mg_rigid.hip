@@ -41,6 +41,7 @@
 #include "mg_internal.h"
 #include "mg_math.h"
 #include "mg_attractor.h"
+#include "mg_contact.h"
 
 #ifdef MG_RIGID1_STAMPS
 // diagnostic build only (tools/kbench_rigid_stamps.py): s_memtime stamps of
@@ -328,8 +329,10 @@ __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, co
 // cached inertia vectors; MULTI = true: several shapes, shift-register slots.
 // ATTR: the attractor-aware build (mg_attractor.h), stepped when a free body of
 // the sim owns an attractor; a body without one runs the same operations as in
-// the plain build.
-template <int MAXC, bool MULTI, bool ATTR, class B>
+// the plain build. CREP: the reporting build, stepped while
+// contact reporting is on: the last substep's slots go to the body's staging
+// record, with the impulses that enter fsum.
+template <int MAXC, bool MULTI, bool ATTR, bool CREP, class B>
 __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const MgRigidArgs& A, int b) {
     constexpr bool CACHE = !MULTI;
     const int nb = A.nb;
@@ -374,6 +377,7 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
 
     q = qnormalize(q);
     V3 fsum = v3(0.0f, 0.0f, 0.0f);
+    int crk = 0;   // CREP: entries staged
 
     for (int st = 0; st < P.substeps; ++st) {
         const S3 Iw = sym_rdrt(qmat(inertia_frame(q, iq)), invI);
@@ -487,6 +491,21 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
                 fsum = G.add2(fsum, sl[j].lt2);
             }
         }
+        if constexpr (CREP) {
+            if (st == P.substeps - 1) {
+                const V3 z3 = v3(0.0f, 0.0f, 0.0f);
+                const int gb = A.crep_body[b];
+#pragma unroll
+                for (int j = 0; j < MAXC; ++j) {
+                    if (sl[j].on && crk < MG_CREP_FREE_CAP) {
+                        // per-point friction rows: the point carries its friction impulse
+                        crep_store(A.crep + b, A.crep_stride, crk, gb, -1, 0, vadd(xc, sl[j].r), G.addn(z3, 1.0f),
+                                   sl[j].s0, sl[j].ln, G.add2(G.add1(z3, sl[j].lt1), sl[j].lt2), sl[j].mu);
+                        crk = crk + 1;
+                    }
+                }
+            }
+        }
 
         // 4. pose update (centre of mass moves by the integrated delta)
         const V3 xc1 = vadd(xc, dx);
@@ -501,6 +520,7 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
     A.cforce[0 * nb + b] = fsum.x * P.inv_dt;
     A.cforce[1 * nb + b] = fsum.y * P.inv_dt;
     A.cforce[2 * nb + b] = fsum.z * P.inv_dt;
+    if constexpr (CREP) A.crep_n[b] = crk;
 }
 
 // ---- single-shape bodies: k_rigid_step1 ------------------------------------
@@ -746,11 +766,17 @@ __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an
 // template floats, then the shape record; shape type < 0 when it has none).
 // R: the ground patch at the step's start (cnt 0: none), at its end on return.
 // at (ATTR builds): this body's attractor record, or null.
-template <bool PACK, bool ATTR, class B>
-__device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const float* T, V3& x, Q4& q, V3& v,
-                                            V3& w, V3& fsum, float invm, V3 invI, Q4 iq, V3 com, bool has_ext,
-                                            V3 fext, V3 text, const float* hulls, float* gp, int gstride,
-                                            const float (&pr)[MG_FP_N], const float* at) {
+// CREP (the reporting builds): cr is the body's staging record
+// (null: a dead lane), crs its stride, gbody the body's global index; the last
+// substep's points and anchors are stored there with the impulses that enter
+// fsum. Returns the number of entries staged.
+template <bool PACK, bool ATTR, bool CREP, class B>
+__device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const float* T, V3& x, Q4& q, V3& v,
+                                           V3& w, V3& fsum, float invm, V3 invI, Q4 iq, V3 com, bool has_ext,
+                                           V3 fext, V3 text, const float* hulls, float* gp, int gstride,
+                                           const float (&pr)[MG_FP_N], const float* at, float* cr = nullptr,
+                                           int crs = 0, int gbody = 0) {
+    int crk = 0;
     const float lin_damp = T[0], ang_damp = T[1], max_lv = T[2], max_av = T[3], grav_on = T[4];
     // the shape record: wide launches read it from the template record (LDS
     // when staged) in each substep's candidate search — registers are scarcer
@@ -893,11 +919,13 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
             // anchor rows at the anchors' body copies; the position sweeps close
             // 80 % of the substep-start drift of their two copies
             ARow an[2];
+            V3 awp[2];   // CREP: the anchors' body copies in the world
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const bool act = a < R.cnt;
                 // formed on every lane, selected (a divergent branch cost more)
                 const V3 wa = vadd(x, qrot(q, R.aA[a]));
+                if constexpr (CREP) awp[a] = wa;
                 const V3 dr = vsub(wa, R.aB[a]);
                 const float kd = 0.8f * P.inv_h;
                 const V3 r = vsel(act, vsub(wa, xc), v3(0.0f, 0.0f, 0.0f));
@@ -981,6 +1009,26 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
                 fsum = G.add1(fsum, an[a].l1);
                 fsum = G.add2(fsum, an[a].l2);
             }
+            if constexpr (CREP) {
+                if (cr && st == P.substeps - 1) {
+                    const V3 z3 = v3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (on[j]) {
+                            crep_store(cr, crs, crk, gbody, -1, 0, cp[j], n0, sl[j].s0, sl[j].ln, z3, mu);
+                            crk = crk + 1;
+                        }
+                    }
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) {
+                        if (a < R.cnt) {
+                            crep_store(cr, crs, crk, gbody, -1, 1, awp[a], n0, 0.0f, 0.0f,
+                                       G.add2(G.add1(z3, an[a].l1), an[a].l2), mu);
+                            crk = crk + 1;
+                        }
+                    }
+                }
+            }
             // a slipping patch lets go (regrown at the next substep)
             const bool one = R.cnt < 2;
             if ((c01 && (c11 || one)) || (c02 && (c12 || one))) R.cnt = 0;
@@ -1012,6 +1060,7 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
             for (int k = 1; k < MG_FP_N; ++k) gp[(size_t)k * gstride] = r[k];
         }
     }
+    return crk;
 }
 
 // Wide launches: __launch_bounds__(64, 3), at most 168 VGPRs, so three waves
@@ -1021,15 +1070,16 @@ __device__ __forceinline__ void rigid_body1(const B& G, const MgStep& P, const f
 // VGPRs and no scratch — at three waves the shape record spilled 36 B/lane
 // (4096 envs: 13.2 us against 13.5 with the record in LDS and 13.5 at either
 // budget, same-box A/B, profiles/r05_ab_rigid_shape_regs.jsonl). The general
-// ground basis needs more registers: two waves.
+// ground basis needs more registers: two waves. So do the reporting builds
+// (CREP): at three waves their staging stores spilled 25 to 47 registers.
 #ifndef MG_RIGID1_ROUND_WAVES
 #define MG_RIGID1_ROUND_WAVES 2
 #endif
 #ifndef MG_RIGID1_WIDE_WAVES
 #define MG_RIGID1_WIDE_WAVES 3
 #endif
-template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false>
-__global__ void __launch_bounds__(64, UPZ && WIDE ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
+template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false, bool CREP = false>
+__global__ void __launch_bounds__(64, UPZ && WIDE && !CREP ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
 k_rigid_step1(MgStep P, MgRigidArgs A) {
     extern __shared__ float s_trec[];
     const int i = (WIDE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 64 + threadIdx.x;
@@ -1191,16 +1241,28 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
         const int ai = A.attr_idx[b];
         if (live && ai >= 0) at = A.attr + (size_t)ai * MG_ATTR_N;
     }
+    // reporting builds: this body's staging record and its global index
+    float* cr = nullptr;
+    int gbody = 0, crk = 0;
+    if constexpr (CREP) {
+        if (live) {
+            cr = A.crep + b;
+            gbody = A.crep_body[b];
+        }
+    }
     if constexpr (UPZ) {
-        rigid_body1<!WIDE, ATTR>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text,
-                                 A.hulls, gp, A.gstride, pr, at);
+        crk = rigid_body1<!WIDE, ATTR, CREP>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr,
+                                             fext, text, A.hulls, gp, A.gstride, pr, at, cr, A.crep_stride, gbody);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        rigid_body1<!WIDE, ATTR>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext, text, A.hulls,
-                                 gp, A.gstride, pr, at);
+        crk = rigid_body1<!WIDE, ATTR, CREP>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext,
+                                             text, A.hulls, gp, A.gstride, pr, at, cr, A.crep_stride, gbody);
+    }
+    if constexpr (CREP) {
+        if (live) A.crep_n[b] = crk;
     }
     // the output addresses are recomputed here (an opaque copy of the slot)
     // rather than kept live in registers across the frame
@@ -1272,19 +1334,19 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     }
 }
 
-template <bool UPZ, int MAXC, bool MULTI, bool ATTR>
+template <bool UPZ, int MAXC, bool MULTI, bool ATTR, bool CREP = false>
 __global__ void __launch_bounds__(64) k_rigid_step(MgStep P, MgRigidArgs A) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A.nf) return;
     const int b = A.free_ids ? A.free_ids[i] : i;
     if constexpr (UPZ) {
-        rigid_body<MAXC, MULTI, ATTR>(BasisZ{}, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR, CREP>(BasisZ{}, P, A, b);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        rigid_body<MAXC, MULTI, ATTR>(G, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR, CREP>(G, P, A, b);
     }
 }
 
@@ -1330,6 +1392,42 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         A2.ext = A.ext ? A.ext + A.nf1 : nullptr;
         A2.cforce = A.cforce + A.nf1;
         A2.attr_idx = A.attr_idx ? A.attr_idx + A.nf1 : nullptr;
+        A2.crep = A.crep ? A.crep + A.nf1 : nullptr;
+        A2.crep_n = A.crep_n ? A.crep_n + A.nf1 : nullptr;
+        A2.crep_body = A.crep_body ? A.crep_body + A.nf1 : nullptr;
+    }
+    if (A.crep) {
+        // contact reporting is on: the reporting builds (template records read
+        // from global memory, the slot's indices from their separate arrays:
+        // where they live changes no value)
+        const bool at = A.attr_idx != nullptr;
+        A1.slot_rec = nullptr;
+        if (A1.nf > 0) {
+            const int blocks = (A1.nf + 63) / 64;
+            // the threshold of the plain launches, kept on purpose although the wide
+            // reporting build holds two waves per SIMD, not three: which bodies
+            // step in which form (and so every value) is then the same with
+            // reporting on and off
+            const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
+#define MG_K1C(U, W, T) MG_LAUNCH((k_rigid_step1<U, false, W, T, false, true>), dim3(blocks), dim3(64), 0, s, P, A1)
+#define MG_K1C_T(U, W) do { if (at) MG_K1C(U, W, true); else MG_K1C(U, W, false); } while (0)
+            if (upz && wide) MG_K1C_T(true, true);
+            else if (upz) MG_K1C_T(true, false);
+            else if (wide) MG_K1C_T(false, true);
+            else MG_K1C_T(false, false);
+#undef MG_K1C_T
+#undef MG_K1C
+        }
+        if (A2.nf > 0) {
+            const int blocks = (A2.nf + 63) / 64;
+#define MG_K2C(U, T) MG_LAUNCH((k_rigid_step<U, MG_MAX_CONTACTS, true, T, true>), dim3(blocks), dim3(64), 0, s, P, A2)
+            if (upz && at) MG_K2C(true, true);
+            else if (upz) MG_K2C(true, false);
+            else if (at) MG_K2C(false, true);
+            else MG_K2C(false, false);
+#undef MG_K2C
+        }
+        return hipGetLastError();
     }
     if (A1.nf > 0) {
         const int blocks = (A1.nf + 63) / 64;

@@ -294,6 +294,32 @@ struct mg_sim {
     float* d_sens_out = nullptr;          // [n_sens][6]
     float* d_ctorque = nullptr;           // [3][nb], allocated with the first sensor table
 
+    // rigid contact list (mg_set_contact_reporting, mg_contact.hip, DESIGN.md
+    // §3.14). While crep_on the reporting builds of the step kernels fill the
+    // staging records and k_contact_compact packs them into d_crep_out; the
+    // buffers are allocated by the call that turns reporting on. crep_valid: a
+    // reporting simulate has run since. The header (true total, stored total)
+    // is kept on the device and in mapped host memory, which the refresh reads
+    // after waiting for the stream.
+    bool crep_on = false, crep_valid = false;
+    int crep_capacity = 0;
+    std::vector<int> h_slot_env;          // [nb] internal slot of an actor root -> env
+    std::vector<int> h_pile_env;          // [n_pile] pile env -> env
+    std::vector<int> h_cenv_env, h_cenv_row;   // coupled env k (env order) -> env, its row of d_env
+    float* d_crep_cenv = nullptr;         // [2 MG_ENV_MAXCT_WIDE][MG_CREP_N][n_coupled], column = row of d_env
+    int* d_crep_cenv_n = nullptr;         // [n_coupled]
+    int* d_crep_col = nullptr;            // [n_coupled] coupled env k -> its column
+    float* d_crep_pile = nullptr;         // [MG_PILE_MAXPT][MG_CREP_N][n_pile]
+    int* d_crep_pile_n = nullptr;         // [n_pile]
+    float* d_crep_free = nullptr;         // [MG_CREP_FREE_CAP][MG_CREP_N][nf_rigid]
+    int* d_crep_free_n = nullptr;         // [nf_rigid]
+    int* d_crep_env = nullptr;            // [owners] owner -> env
+    int* d_crep_blk = nullptr;            // [blocks] pass 1 -> pass 2
+    mg_rigid_contact* d_crep_out = nullptr;
+    int* d_crep_hdr = nullptr;            // [2]
+    int* h_crep_hdr = nullptr;            // [2] mapped, page-locked
+    int* d_crep_hdr_alias = nullptr;      // its device address
+
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false;          // mg_set_kernel_timing: events around eager launches
     bool timed_step = false;      // the last simulate recorded ev_begin / ev_end
@@ -522,9 +548,11 @@ void free_all(mg_sim* s) {
                     s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_slot_rec, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
                     s->d_dof_props, s->d_artic, s->d_artic_step, s->d_env, s->d_pairs, s->d_fpatch, s->d_gpatch, s->d_chain_uni, s->d_fp_mask, s->d_env_carry, s->d_env_ctab, s->d_link_f, s->d_link_i, s->d_stage, s->d_stage_idx, s->d_host_out,
                     s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams,
-                    s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out, s->d_ctorque};
+                    s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out, s->d_ctorque,
+                    s->d_crep_cenv, s->d_crep_cenv_n, s->d_crep_col, s->d_crep_free, s->d_crep_free_n, s->d_crep_pile, s->d_crep_pile_n, s->d_crep_env, s->d_crep_blk, s->d_crep_out, s->d_crep_hdr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (s->h_crep_hdr) (void)hipHostFree(s->h_crep_hdr);
 }
 
 }  // namespace
@@ -648,6 +676,8 @@ static hipError_t chain_uni_upload(mg_sim* s) {
 int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     if (!s || !m) return fail(MG_ERR_ARG, "null argument");
     if (s->uploaded) return fail(MG_ERR_STATE, "model already uploaded");
+    s->h_pile_env.clear();
+    s->h_cenv_env.clear();
     if (m->num_bodies < 0 || m->num_actors < 0 || m->num_dofs < 0) return fail(MG_ERR_ARG, "negative sizes");
     HIP_TRY(hipSetDevice(s->device));
     const int nb = m->num_bodies, na = m->num_actors, nd = m->num_dofs;
@@ -828,6 +858,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
                     pile_slots.insert(pile_slots.end(), slots.begin(), slots.end());
                 }
                 pile_rows.push_back(row);
+                s->h_pile_env.push_back(e);
                 continue;
             }
             if (art.size() > 1 || fr.size() > MG_ENV_MAXF || stc.size() > MG_ENV_MAXS)
@@ -945,6 +976,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
             }
             row[15] = (int)(pairs.size() / 4) - row[14];
             env_rows.push_back(row);
+            s->h_cenv_env.push_back(e);
             env_tmpl.push_back(tmpl);
         }
     }
@@ -1128,6 +1160,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     s->env_groups.clear();
     s->cenv_ctab_off.assign(env_rows.size(), -1);
     s->cenv_ctab_n.assign(env_rows.size(), 0);
+    s->h_cenv_row.assign(env_rows.size(), 0);
     // (and by lane width: an env of more than 16 links or velocity slots runs
     // 64 lanes wide, mg_env.hip; the oracle decides per env the same way)
     for (int t = -1; t < m->num_artic_tmpls; ++t)
@@ -1156,6 +1189,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
             s->cenv_ctab_off[r] = (long long)g.offset * mg_env_ctab_floats() +
                                   (long long)g.count * mg_env_ctab_record_floats(wide);
             s->cenv_ctab_n[r] = mg_env_ctab_record_floats(wide);
+            s->h_cenv_row[r] = g.offset + g.count;
             g.count++;
         }
         if (g.count > 0) s->env_groups.push_back(g);
@@ -1305,6 +1339,10 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         // (MG_FUSE_STEP_OUT): internal slot -> rigid-body row / actor row
         std::vector<int> slot_actor(nb, -1);
         for (int a = 0; a < na; ++a) slot_actor[root_int[a]] = a;
+        // the env of each actor root's slot (the contact list's env column)
+        s->h_slot_env.assign((size_t)std::max(nb, 1), 0);
+        if (m->actor_coll)
+            for (int a = 0; a < na; ++a) s->h_slot_env[root_int[a]] = m->actor_coll[(size_t)a * MG_ACOLL_N + 0];
         HIP_TRY(dalloc(&s->d_slot_global, (size_t)std::max(nb, 1)));
         HIP_TRY(h2d(s->d_slot_global, order.data(), (size_t)nb * sizeof(int)));
         HIP_TRY(dalloc(&s->d_slot_actor, (size_t)std::max(nb, 1)));
@@ -1486,11 +1524,11 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     }
     const unsigned long long step_cid = capture_id(st);
     const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->step_out_ok &&
-                          s->attrs.empty() && (s->bind_root || s->bind_rb || s->bind_dof);
+                          s->attrs.empty() && !s->crep_on && (s->bind_root || s->bind_rb || s->bind_dof);
     // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
     // write into the library's own buffer, so no caller-visible tensor changes
     float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && step_cid == 0;
+    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && !s->crep_on && step_cid == 0;
     float* ho_root = host_out ? ho_base : nullptr;
     float* ho_rb = host_out ? ho_base + (size_t)s->na * MG_STATE_N : nullptr;
     float* ho_dof = host_out && s->nd ? ho_base + (size_t)(s->na + s->nb) * MG_STATE_N : nullptr;
@@ -1576,6 +1614,14 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.attr_idx = s->d_attr_idx;
             A.attr = s->d_attr;
         }
+        if (s->crep_on) {
+            // the reporting builds, force-reporting builds too
+            A.crep = s->d_crep_cenv + g.offset;
+            A.crep_n = s->d_crep_cenv_n + g.offset;
+            A.crep_body = s->d_slot_global;
+            A.crep_stride = std::max(s->n_coupled, 1);
+            A.dof_frc = s->d_dof_frc;
+        }
         if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) {
             // the contact-moment builds, which are force-reporting builds too
             // (rows of DOFs that do not report are masked by the refresh)
@@ -1593,6 +1639,11 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
+        if (s->crep_on) {   // the reporting build
+            A.crep = s->d_crep_pile;
+            A.crep_n = s->d_crep_pile_n;
+            A.crep_body = s->d_slot_global;
+        }
         hipError_t e = mg_launch_pile_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
     }
@@ -1610,6 +1661,12 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         if (s->n_attr_free > 0) {
             A.attr_idx = s->d_attr_idx;
             A.attr = s->d_attr;
+        }
+        if (s->crep_on) {   // the reporting builds
+            A.crep = s->d_crep_free;
+            A.crep_n = s->d_crep_free_n;
+            A.crep_body = s->d_slot_global;
+            A.crep_stride = std::max(s->nf_rigid, 1);
         }
         bool reads_root_in = false;
         if (s->pend_root) {   // the deferred root set, read by the step kernel
@@ -1647,6 +1704,38 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         if (s->bind_root) { s->out_gen = s->state_gen; s->out_cap = step_cid; }
         if (s->bind_rb) { s->rb_gen = s->state_gen; s->rb_cap = step_cid; }
         if (s->bind_dof) { s->dof_gen = s->dof_sgen; s->dof_cap = step_cid; }
+    }
+    if (s->crep_on) {
+        // the contact list of this frame: the staging records packed in owner order
+        MgContactArgs C{};
+        C.fam[0].n = s->nf_rigid;
+        C.fam[0].cap = MG_CREP_FREE_CAP;
+        C.fam[0].stride = std::max(s->nf_rigid, 1);
+        C.fam[0].stage = s->d_crep_free;
+        C.fam[0].count = s->d_crep_free_n;
+        C.fam[0].env = s->d_crep_env;
+        C.fam[1].n = s->n_coupled;
+        C.fam[1].cap = 2 * MG_ENV_MAXCT_WIDE;
+        C.fam[1].stride = std::max(s->n_coupled, 1);
+        C.fam[1].stage = s->d_crep_cenv;
+        C.fam[1].count = s->d_crep_cenv_n;
+        C.fam[1].env = s->d_crep_env + s->nf_rigid;
+        C.fam[1].col = s->d_crep_col;
+        C.fam[2].n = s->n_pile;
+        C.fam[2].cap = MG_PILE_MAXPT;
+        C.fam[2].stride = std::max(s->n_pile, 1);
+        C.fam[2].stage = s->d_crep_pile;
+        C.fam[2].count = s->d_crep_pile_n;
+        C.fam[2].env = s->d_crep_env + s->nf_rigid + s->n_coupled;
+        C.n_own = s->nf_rigid + s->n_coupled + s->n_pile;
+        C.nblk = (C.n_own + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK;
+        C.blk_sum = s->d_crep_blk;
+        C.out = s->d_crep_out;
+        C.capacity = s->crep_capacity;
+        C.header = s->d_crep_hdr;
+        C.header_host = s->d_crep_hdr_alias;
+        HIP_TRY(mg_launch_contact_compact(C, st));
+        s->crep_valid = true;
     }
     // the force sensors' readings, before the applied wrenches are cleared
     if (s->n_sens > 0) HIP_TRY(mg_launch_force_sensor(sensor_args(s, P), st));
@@ -1950,7 +2039,9 @@ int32_t mg_discard_pending_sets(mg_sim* s) {
     return MG_OK;
 }
 
-int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && s->step_out_ok && s->attrs.empty() ? 1 : 0; }
+int32_t mg_step_out_supported(mg_sim* s) {
+    return s && s->uploaded && s->step_out_ok && s->attrs.empty() && !s->crep_on ? 1 : 0;
+}
 
 int32_t mg_last_set_deferred(mg_sim* s) { return s ? s->last_set_deferred : 0; }
 
@@ -2301,6 +2392,97 @@ int32_t mg_refresh_force_sensor(mg_sim* s, float* dst, int32_t dst_host, void* s
 }
 
 int32_t mg_num_force_sensors(mg_sim* s) { return s ? (int32_t)s->sensors.size() : 0; }
+
+// ---- rigid contact list ----------------------------------------
+int32_t mg_set_contact_reporting(mg_sim* s, int32_t on, int32_t capacity) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (capacity < 0) return fail(MG_ERR_ARG, "negative contact capacity %d", capacity);
+    // the switch decides which kernels a simulate launches: a graph captured
+    // before the call would replay the old launches
+    if (s->capturing)
+        return fail(MG_ERR_STATE, "contact reporting changed after the step was captured into a graph (the replays "
+                    "keep the old launches); call it before the capture, or after an eager simulate");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    void* old[] = {s->d_crep_cenv, s->d_crep_cenv_n, s->d_crep_col, s->d_crep_free, s->d_crep_free_n, s->d_crep_pile, s->d_crep_pile_n, s->d_crep_env, s->d_crep_blk, s->d_crep_out, s->d_crep_hdr};
+    for (void* p : old)
+        if (p) (void)hipFree(p);
+    s->d_crep_free = nullptr; s->d_crep_free_n = nullptr; s->d_crep_env = nullptr; s->d_crep_blk = nullptr;
+    s->d_crep_pile = nullptr; s->d_crep_pile_n = nullptr;
+    s->d_crep_cenv = nullptr; s->d_crep_cenv_n = nullptr; s->d_crep_col = nullptr;
+    s->d_crep_out = nullptr; s->d_crep_hdr = nullptr;
+    s->crep_on = false;
+    s->crep_valid = false;
+    s->crep_capacity = 0;
+    if (!on) return MG_OK;
+    const int nfree = s->nf_rigid, ncenv = s->n_coupled, npile = s->n_pile, nown = nfree + ncenv + npile;
+    const int cenv_cap = 2 * MG_ENV_MAXCT_WIDE;
+    const long long worst = (long long)nfree * MG_CREP_FREE_CAP + (long long)ncenv * cenv_cap +
+                            (long long)npile * MG_PILE_MAXPT;
+    if (worst > (1ll << 30)) return fail(MG_ERR_UNSUPPORTED, "contact reporting: %lld staged entries", worst);
+    const int cap = capacity > 0 ? capacity : (int)std::max(worst, 1ll);
+    HIP_TRY(dalloc(&s->d_crep_free, (size_t)std::max(nfree, 1) * MG_CREP_FREE_CAP * MG_CREP_N));
+    HIP_TRY(dalloc(&s->d_crep_free_n, (size_t)std::max(nfree, 1)));
+    HIP_TRY(dalloc(&s->d_crep_cenv, (size_t)std::max(ncenv, 1) * cenv_cap * MG_CREP_N));
+    HIP_TRY(dalloc(&s->d_crep_cenv_n, (size_t)std::max(ncenv, 1)));
+    HIP_TRY(dalloc(&s->d_crep_col, (size_t)std::max(ncenv, 1)));
+    HIP_TRY(hipMemset(s->d_crep_cenv_n, 0, (size_t)std::max(ncenv, 1) * sizeof(int)));
+    if (ncenv > 0)
+        HIP_TRY(hipMemcpy(s->d_crep_col, s->h_cenv_row.data(), (size_t)ncenv * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(dalloc(&s->d_crep_pile, (size_t)std::max(npile, 1) * MG_PILE_MAXPT * MG_CREP_N));
+    HIP_TRY(dalloc(&s->d_crep_pile_n, (size_t)std::max(npile, 1)));
+    HIP_TRY(dalloc(&s->d_crep_env, (size_t)std::max(nown, 1)));
+    HIP_TRY(dalloc(&s->d_crep_blk, (size_t)(nown + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK + 1));
+    HIP_TRY(dalloc(&s->d_crep_out, (size_t)cap));
+    HIP_TRY(dalloc(&s->d_crep_hdr, 2));
+    if (!s->h_crep_hdr) {
+        HIP_TRY(hipHostMalloc((void**)&s->h_crep_hdr, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void**)&s->d_crep_hdr_alias, s->h_crep_hdr, 0));
+    }
+    s->h_crep_hdr[0] = 0;
+    s->h_crep_hdr[1] = 0;
+    HIP_TRY(hipMemset(s->d_crep_free_n, 0, (size_t)std::max(nfree, 1) * sizeof(int)));
+    HIP_TRY(hipMemset(s->d_crep_pile_n, 0, (size_t)std::max(npile, 1) * sizeof(int)));
+    HIP_TRY(hipMemset(s->d_crep_hdr, 0, 2 * sizeof(int)));
+    // owner -> env: free bodies are their own actors' roots (owner = storage
+    // slot), then the coupled envs and the pile envs, each by env index
+    if (nown > 0) {
+        std::vector<int> env(s->h_slot_env.begin(), s->h_slot_env.begin() + nfree);
+        env.insert(env.end(), s->h_cenv_env.begin(), s->h_cenv_env.end());
+        env.insert(env.end(), s->h_pile_env.begin(), s->h_pile_env.end());
+        HIP_TRY(hipMemcpy(s->d_crep_env, env.data(), (size_t)nown * sizeof(int), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    s->crep_capacity = cap;
+    s->crep_on = true;
+    return MG_OK;
+}
+
+int32_t mg_contact_reporting(mg_sim* s) { return s && s->crep_on ? 1 : 0; }
+
+int32_t mg_refresh_rigid_contacts(mg_sim* s, mg_rigid_contact* dst, int32_t cap, int32_t dst_host, int32_t* total,
+                                  void* stream) {
+    if (total) *total = 0;
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (cap < 0 || (!dst && cap > 0)) return fail(MG_ERR_ARG, "bad destination");
+    if (!s->crep_on || !s->crep_valid) return 0;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone) return fail(MG_ERR_STATE, "mg_refresh_rigid_contacts while capturing");
+    // the record count is the compaction's: wait for it, then copy that many
+    HIP_TRY(hipStreamSynchronize(st));
+    const int all = s->h_crep_hdr[0], stored = std::min(s->h_crep_hdr[1], s->crep_capacity);
+    if (total) *total = all;
+    const int n = std::max(std::min(stored, cap), 0);
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(dst, s->d_crep_out, (size_t)n * sizeof(mg_rigid_contact),
+                               dst_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+        if (dst_host) HIP_TRY(hipStreamSynchronize(st));
+    }
+    return n;
+}
 
 int32_t mg_refresh_net_contact_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");

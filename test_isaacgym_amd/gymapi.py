@@ -1460,6 +1460,117 @@ class Gym:
         if sim.native:
             N.check(N.lib.mg_set_light(sim.native, ctypes.byref(L)), "mg_set_light")
 
+    # ---- rigid contact list (include/migym.h)
+    def set_rigid_contact_reporting(self, sim, on, max_contacts=0):
+        """migym extension (not in Isaac Gym): keep the per-contact records of
+        each simulate's last substep for get_rigid_contacts (the reporting
+        builds of the step kernels; off by default). max_contacts bounds the
+        list (0: the scene's worst case); records past it are dropped. Call it
+        before the first simulate, or the first get_*_rigid_contacts turns it on
+        and reads an empty list. Raises MigymError where the library refuses
+        (after a simulate captured into a graph)."""
+        sim.set_contact_reporting(on, max_contacts)
+        return True
+
+    def get_rigid_contact_reporting(self, sim):
+        return bool(sim.contact_reporting[0])
+
+    def _rigid_contacts(self, sim, env=None):
+        out = np.zeros(0, dtype=_T.RigidContact.dtype)
+        if not sim.contact_reporting[0]:
+            # Isaac Gym has no switch: the first query turns reporting on; the
+            # last simulate recorded nothing, so this read is empty
+            sim.set_contact_reporting(True, sim.contact_reporting[1])
+            if not sim.contact_first_query:
+                sim.contact_first_query = True
+                print("*** migym: get_rigid_contacts: contact reporting is now on; the list starts with the next "
+                      "simulate (set_rigid_contact_reporting before the first simulate avoids this empty read)",
+                      file=sys.stderr)
+            return out
+        if not sim.finalized or sim.native is None:
+            return out
+        rec, _ = sim.rigid_contact_records()
+        if env is not None:
+            rec = rec[rec["env"] == env.index]
+        if len(rec) == 0:
+            return out
+        rb, _ = self._host_state(sim)
+        kind = sim.model_arrays["body_kind"]
+        first = np.array([e.actors[0].global_body if e.actors else 0 for e in sim.envs], dtype=np.int64)
+        origin = np.array([e.origin for e in sim.envs], dtype=np.float64).reshape(-1, 3)
+        ei = rec["env"].astype(np.int64)
+        p = rec["p"].astype(np.float64)
+        n = rec["n"].astype(np.float64)
+        out = np.zeros(len(rec), dtype=_T.RigidContact.dtype)
+        out["env0"] = rec["env"]
+        out["env1"] = rec["env"]
+        for name, lp in (("body0", "localPos0"), ("body1", "localPos1")):
+            g = rec[name].astype(np.int64)
+            out[name] = np.where(g >= 0, g - first[ei], -1)
+            # the point in the body's frame at the end of the step; the env point
+            # for the ground and for static bodies
+            loc = p - origin[ei]
+            gi = np.clip(g, 0, max(sim.num_bodies - 1, 0))
+            dyn = (g >= 0) & (kind[gi] != N.MG_BODY_STATIC)
+            if dyn.any():
+                x, q = rb[gi[dyn], 0:3].astype(np.float64), rb[gi[dyn], 3:7].astype(np.float64)
+                d = p[dyn] - x
+                # rotate by the conjugate: v' = v + 2 w (u x v) + 2 u x (u x v), u = -q.xyz
+                u, w = -q[:, 0:3], q[:, 3:4]
+                t = 2.0 * np.cross(u, d)
+                loc[dyn] = d + w * t + np.cross(u, t)
+            for k, c in enumerate("xyz"):
+                out[lp][c] = loc[:, k]
+        for k, c in enumerate("xyz"):
+            out["normal"][c] = rec["n"][:, k]
+        out["minDist"] = rec["separation"]
+        out["lambda"] = rec["lambda"]
+        out["friction"] = rec["mu"]
+        # friction impulse on (t1, t2): t1 = normalize(n x x^) (y^ when n is
+        # within |n x x^| < 0.1 of the x axis), t2 = n x t1
+        ax = np.tile(np.array([1.0, 0.0, 0.0]), (len(rec), 1))
+        t1 = np.cross(n, ax)
+        near = np.linalg.norm(t1, axis=1) < 0.1
+        if near.any():
+            t1[near] = np.cross(n[near], np.array([0.0, 1.0, 0.0]))
+        t1 /= np.maximum(np.linalg.norm(t1, axis=1, keepdims=True), 1e-30)
+        t2 = np.cross(n, t1)
+        f = rec["fimp"].astype(np.float64)
+        out["lambdaFriction"]["x"] = (f * t1).sum(axis=1)
+        out["lambdaFriction"]["y"] = (f * t2).sum(axis=1)
+        return out
+
+    def get_env_rigid_contacts(self, env):
+        """The env's records of the contact list (RigidContact.dtype; DESIGN.md
+        §3.14): the contact points and friction anchors of the last simulate's
+        last substep. An anchor entry follows the point entries of its body and
+        has lambda == 0 with a non-zero lambdaFriction."""
+        return self._rigid_contacts(env.sim, env)
+
+    def get_rigid_contacts(self, sim):
+        """Every env's records, in the list's order (get_env_rigid_contacts)."""
+        return self._rigid_contacts(sim)
+
+    def _contact_forces(self, sim, first, count):
+        out = np.zeros(count, dtype=Vec3.dtype)
+        if not sim.finalized or sim.native is None or sim.num_bodies == 0:
+            return out
+        ncf = np.zeros((sim.num_bodies, 3), dtype=np.float32)
+        N.check(N.lib.mg_refresh_net_contact_force(sim.native, ncf.ctypes.data, 1, sim.stream()),
+                "mg_refresh_net_contact_force")
+        for k, c in enumerate("xyz"):
+            out[c] = ncf[first:first + count, k]
+        return out
+
+    def get_env_rigid_contact_forces(self, env):
+        """The net contact force on each rigid body of the env (Vec3 records)."""
+        first = env.actors[0].global_body if env.actors else 0
+        return self._contact_forces(env.sim, first, env.num_bodies)
+
+    def get_rigid_contact_forces(self, sim):
+        sim._assign_indices()
+        return self._contact_forces(sim, 0, sim.num_bodies)
+
     def draw_env_rigid_contacts(self, viewer, env, color, scale, flag):
         pass
 
