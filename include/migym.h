@@ -86,7 +86,10 @@ extern "C" {
 #define MG_TBODY_F_N       8  /* lin_damp, ang_damp, max_lin_vel, max_ang_vel, gravity_on, pad[3] */
 #define MG_TBODY_I_N       4  /* shape_start, shape_count, pad, pad */
 #define MG_SHAPE_STRIDE   16  /* type, size[3], p[3], q[4], friction, restitution, pad[3] */
-#define MG_DOFPROP_N      12  /* mode, kp, kd, effort, max_vel, lower, upper, has_limits, armature, friction, pad[2] */
+#define MG_DOFPROP_N      12  /* mode, kp, kd, effort, max_vel, lower, upper, has_limits, armature, friction, pad[2];
+                                  friction: the joint's Coulomb limit tau_f >= 0 on its own generalized force
+                                  (N m revolute, N prismatic; URDF <dynamics friction>, MJCF frictionloss),
+                                  solved as an implicit velocity-level row per substep */
 #define MG_LINK_F_N       16  /* joint origin p[3], q[4] (parent link frame), axis[3] (joint frame),
                                   ball place [1] (0: none, 1..3: a ball joint's links), pad[5] */
 /* parent (local, -1 root), joint type, dof (local, -1 none), body (local body index of the
@@ -263,8 +266,20 @@ int32_t     mg_set_dof_velocity_target(mg_sim* sim, const float* src, int32_t sr
 int32_t     mg_set_dof_actuation_force(mg_sim* sim, const float* src, int32_t src_host,
                                        const int32_t* idx, int32_t n_idx, void* stream);
 /* DOF drive properties of every DOF, [num_dofs][MG_DOFPROP_N] host array
- * (gym.set_actor_dof_properties after prepare_sim). */
+ * (gym.set_actor_dof_properties after prepare_sim). Field 9, friction, decides
+ * which kernels step a DOF (the joint-friction builds step the uncoupled
+ * instances and the coupled groups that hold a DOF with friction > 0): negative
+ * or non-finite friction is MG_ERR_ARG; a table that changes this routing after
+ * a simulate was captured into a graph is MG_ERR_STATE and changes nothing.
+ * Friction together with attractors, force sensors or contact reporting on the
+ * same group is refused by mg_simulate (MG_ERR_UNSUPPORTED, naming the actor). */
 int32_t     mg_set_dof_props(mg_sim* sim, const float* props_host);
+/* Joint friction routing of the current DOF property table: out[0] DOFs with
+ * friction > 0, out[1] uncoupled articulation instances stepped by the lanes
+ * joint-friction launch, out[2] envs of the coupled groups stepped by the
+ * joint-friction builds. All 0: every kernel launched is a friction-free one.
+ * While out[0] > 0 mg_step_out_supported is 0. */
+int32_t     mg_joint_friction_stats(mg_sim* sim, int32_t out[3]);
 /* gym.apply_rigid_body_force_tensors(sim, forces, torques, space): (num_bodies,3)
  * each or NULL; space 0 = global (ENV_SPACE/GLOBAL), 1 = local (LOCAL_SPACE).
  * Applied at the body's centre of mass during the next simulate only. */

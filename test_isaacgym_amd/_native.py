@@ -211,6 +211,7 @@ def _load():
         "mg_set_contact_reporting": (i32, [vp, i32, i32]),
         "mg_contact_reporting": (i32, [vp]),
         "mg_refresh_rigid_contacts": (i32, [vp, vp, i32, i32, vp, vp]),
+        "mg_joint_friction_stats": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -240,6 +241,7 @@ EXPORTED_SYMBOLS = (
     "mg_enable_dof_forces", "mg_refresh_dof_force", "mg_num_dof_force_dofs",
     "mg_set_force_sensors", "mg_refresh_force_sensor", "mg_num_force_sensors",
     "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
+    "mg_joint_friction_stats",
 )
 
 

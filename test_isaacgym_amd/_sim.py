@@ -836,6 +836,15 @@ class Sim:
                     "mg_refresh_force_sensor")
         return out[index]
 
+    def joint_friction_stats(self):
+        """(friction DOFs, instances in the lanes friction launch, envs of
+        coupled friction groups) of the current DOF properties: which
+        joint-friction kernels the next simulate launches."""
+        out = (ctypes.c_int32 * 3)()
+        N.check(N.lib.mg_joint_friction_stats(self.require_native("joint_friction_stats"), out),
+                "mg_joint_friction_stats")
+        return tuple(int(v) for v in out)
+
     def require_native(self, what):
         self.finalize()
         if self.native is None:

@@ -1078,6 +1078,43 @@ __device__ __forceinline__ void meff_world(const MgEnvArgs& A, EnvLds<MAXL, G>& 
     }
 }
 
+// Joint friction rows, one Gauss-Seidel sweep in DOF order,
+// shared by k_env_step and k_artic_lanes. Row d is owned by lane d: its
+// impulse jl, its box jlim = h tau_f (0: no row) and jk = 1 / (M_eff^-1)_dd stay
+// in that lane's registers, so the rows take no slot of the contact table. The
+// owner solves its row towards velocity 0 within the box, its impulse step is
+// broadcast to the env (DPP / readlane), and every articulation slot moves by
+// its entry of column d of M_eff^-1 — mcol[d] of lane ln, the matrix being
+// symmetric. NA: the articulation's velocity slots (the root's six included).
+// on: the env holds a friction row (an env without one keeps its bits: its
+// lanes run the broadcasts and change nothing).
+template <int ND, int G>
+__device__ __forceinline__ void jfr_sweep(float& uv, float& jl, float jlim, float jk, const float (&mcol)[ND], int ln,
+                                          int DA, int NA, bool on) {
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        if (d < DA) {
+            float dl = 0.0f;
+            if (ln == d && jlim > 0.0f) {
+                const float nl = fminf(fmaxf(jl + jk * (0.0f - uv), -jlim), jlim);
+                dl = nl - jl;
+                jl = nl;
+            }
+            dl = bcastg<G>(dl, d);
+            if (on && ln < NA) uv = uv + mcol[d] * dl;
+        }
+    }
+}
+// lane ln's diagonal entry of M_eff^-1, as the row's 1 / that (0: no response)
+template <int ND>
+__device__ __forceinline__ float jfr_rowk(const float (&mcol)[ND], int ln) {
+    float dd = 0.0f;
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+        if (k == ln) dd = mcol[k];
+    return dd > 0.0f ? 1.0f / dd : 0.0f;
+}
+
 // The template's link constants (joint frames, axes, parents, DOF indices) in
 // LDS for the whole kernel: the serial loops of the kinematic scan and the
 // inward / outward passes read them per link, and from HBM / L2 every such read
@@ -1478,7 +1515,9 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
 // mg_env_crep.hip), launched while contact reporting is on: the frame's last
 // substep leaves the env's contacts and anchors, with their final impulses, in
 // its staging record. They are force-reporting builds too, as the SENS ones.
-template <int MAXL, int G, bool ATTR, bool FRC, bool SENS = false, bool CREP = false>
+// JFR: the joint-friction builds (mg_env_jfr.hip), launched for
+// a group whose envs hold a DOF with friction > 0. Force-reporting builds too.
+template <int MAXL, int G, bool ATTR, bool FRC, bool SENS = false, bool CREP = false, bool JFR = false>
 __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     constexpr int MAXCT = maxct<G>();
@@ -1582,6 +1621,10 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
     // slot registers
     float qv = 0.0f, uv = 0.0f, dp = 0.0f;
     DofC dc = {};
+    // JFR: this DOF's friction box h tau_f (0: no row), its row's impulse and
+    // 1 / (M_eff^-1)_dd; jfr_env: the env holds a friction row
+    [[maybe_unused]] float jlim = 0.0f, jl = 0.0f, jk = 0.0f;
+    [[maybe_unused]] bool jfr_env = false;
     if (is_dof) {
         const int gd = d0 + ln;
         qv = first ? A.dof_pos[gd] : cyl[0];
@@ -1595,6 +1638,7 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
         dc.hi = pr[6 * nd + gd];
         dc.haslim = pr[7 * nd + gd] != 0.0f;
         dc.arm = pr[8 * nd + gd];
+        if constexpr (JFR) jlim = h * pr[9 * nd + gd];
         dc.tpos = A.dof_tpos[gd];
         dc.tvel = A.dof_tvel[gd];
         dc.force = A.dof_force[gd];
@@ -1779,7 +1823,15 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
 
         // ================= 3. rows
         const bool link_rows = live && S.link_rows != 0;
-        if (LA > 0 && __any(link_rows)) meff_world<ATTR, MAXL, ND, G>(A, S, link_rows, ln, LA, DA, x0, lk, mcol, b0, h);
+        if constexpr (JFR) {
+            // the friction rows need M_eff^-1 whether or not a link is in contact
+            jfr_env = grp_ballot<G>(jlim > 0.0f, gi) != 0ull;
+            const bool mw = link_rows || jfr_env;
+            if (LA > 0 && __any(mw)) meff_world<ATTR, MAXL, ND, G>(A, S, mw, ln, LA, DA, x0, lk, mcol, b0, h);
+            jk = jfr_rowk<ND>(mcol, ln);
+        } else {
+            if (LA > 0 && __any(link_rows)) meff_world<ATTR, MAXL, ND, G>(A, S, link_rows, ln, LA, DA, x0, lk, mcol, b0, h);
+        }
         PH_MARK(2);
         // this DOF lane's joint axis and origin at the substep start
         const V3 myz = S.zl[mylink], myx = S.xl[mylink];
@@ -1970,6 +2022,8 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
                     }
                 }
             }
+            // the joint friction rows, in DOF order, target velocity 0
+            if constexpr (JFR) jfr_sweep<ND, G>(uv, jl, jlim, jk, mcol, ln, DA, NA, jfr_env);
             // the last position sweep and the velocity sweeps end with the normal
             // rows again: a friction bound the size of a grip cannot drag a body
             // into a unilateral contact that eight Gauss-Seidel sweeps would not
@@ -2252,7 +2306,11 @@ __global__ void __launch_bounds__(64) k_env_step(MgStep P, MgEnvArgs A) {
 // — and the link states by forward kinematics. Restated by
 // oracle/migym_oracle.c:artic_step (aba_world_ + the same integration and
 // outputs).
-template <int MAXL, int G, bool ATTR, bool FRC>
+// JFR: the joint-friction build (mg_env_jfr.hip), launched
+// over the instances that hold a DOF with friction > 0: after the effort-limit
+// attempts M_eff^-1 (meff_world), then the friction rows' npos + nvel sweeps —
+// the coupled step's, with these rows alone — and q' = q + dpos.
+template <int MAXL, int G, bool ATTR, bool FRC, bool JFR = false>
 __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     constexpr int EPW = 64 / G;          // envs per wavefront
     __shared__ EnvLds<MAXL, G> shm[EPW];
@@ -2273,7 +2331,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     const int b0 = ai[0], d0 = ai[1];
     // link l's body is b0 + l * bs: an attractor-owning instance of a chain
     // group keeps the group's blocked layout (row field 3, migym_capi.cpp)
-    const int bs = ATTR ? ai[3] : 1;
+    const int bs = (ATTR || JFR) ? ai[3] : 1;
     if constexpr (ATTR) { A.attr_idx = AA.attr_idx; A.attr = AA.attr; }
     const int nb = A.nb, nd = A.nd;
     const int LA = A.nl, DA = A.ndof;           // launch-uniform (barriers inside)
@@ -2294,6 +2352,15 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     }
     float qv = 0.0f, uv = 0.0f;
     DofC dc = {};
+    [[maybe_unused]] float jlim = 0.0f;   // JFR: this DOF's friction box h tau_f (0: no row)
+    if constexpr (JFR) {
+        // the link of each DOF's joint (meff_world)
+        if (ln == 0)
+            for (int l = 0; l < LA; ++l) {
+                const int dof = A.link_i[l * MG_LINK_I_N + 2];
+                if (dof >= 0) S.dlink[dof] = l;
+            }
+    }
     if (is_dof) {
         const int gd = d0 + ln;
         qv = A.dof_pos[gd];
@@ -2307,6 +2374,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
         dc.hi = pr[6 * nd + gd];
         dc.haslim = pr[7 * nd + gd] != 0.0f;
         dc.arm = pr[8 * nd + gd];
+        if constexpr (JFR) jlim = h * pr[9 * nd + gd];
         dc.tpos = A.dof_tpos[gd];
         dc.tvel = A.dof_tvel[gd];
         dc.force = A.dof_force[gd];
@@ -2318,7 +2386,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     const int bl = ln < LA ? A.link_i[ln * MG_LINK_I_N + 3] : -1;
     LinkC lk = {};
     lk.iq = q4(0.0f, 0.0f, 0.0f, 1.0f);
-    if (ln < L && bl >= 0) lk = load_link(A.mass, nb, ATTR ? b0 + bl * bs : b0 + bl);
+    if (ln < L && bl >= 0) lk = load_link(A.mass, nb, (ATTR || JFR) ? b0 + bl * bs : b0 + bl);
 
     [[maybe_unused]] float facc = 0.0f;   // FRC: sum over the substeps of this DOF's drive force
     for (int st = 0; st < P.substeps; ++st) {
@@ -2345,15 +2413,39 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
         // integrate the joint (DOF lane); a ball joint's three lanes turn its
         // rotation vector by h w together (ball_dof_step, S.dpos as scratch)
         float w = 0.0f, x = 0.0f;
+        [[maybe_unused]] float dp = 0.0f;
+        if constexpr (JFR) {
+            constexpr int ND = MAXL <= 4 ? 4 : (G > 32 ? 32 : G);
+            float mcol[ND];              // column ln of M_eff^-1 (DOF lanes)
+#pragma unroll
+            for (int k = 0; k < ND; ++k) mcol[k] = 0.0f;
+            meff_world<false, MAXL, ND, G>(A, S, live, ln, LA, DA, x0, lk, mcol, b0, h);
+            const float jk = jfr_rowk<ND>(mcol, ln);
+            if (is_dof) {
+                w = uv + h * S.qdd[ln];
+                if (dc.maxv > 0.0f) w = fminf(fmaxf(w, -dc.maxv), dc.maxv);
+            }
+            float jl = 0.0f;
+            for (int it = 0; it < P.npos + P.nvel; ++it) {
+                jfr_sweep<ND, G>(w, jl, jlim, jk, mcol, ln, DA, DA, live);
+                if (it < P.npos) dp = dp + w * P.sub;
+            }
+        }
         if (is_dof) {
-            w = uv + h * S.qdd[ln];
-            if (dc.maxv > 0.0f) w = fminf(fmaxf(w, -dc.maxv), dc.maxv);
-            x = qv + h * w;
+            if constexpr (JFR) {
+                if (dc.maxv > 0.0f) w = fminf(fmaxf(w, -dc.maxv), dc.maxv);
+                x = qv + dp;
+            } else {
+                w = uv + h * S.qdd[ln];
+                if (dc.maxv > 0.0f) w = fminf(fmaxf(w, -dc.maxv), dc.maxv);
+                x = qv + h * w;
+            }
             if (dc.haslim) {
                 if (x < dc.lo) { x = dc.lo; if (w < 0.0f) w = 0.0f; }
                 if (x > dc.hi) { x = dc.hi; if (w > 0.0f) w = 0.0f; }
             }
-            S.dpos[ln] = h * w;
+            if constexpr (JFR) S.dpos[ln] = dp;
+            else S.dpos[ln] = h * w;
             if constexpr (FRC) facc += drive_force(dc.eff, S.tau0[ln], S.imp[ln], uv, w, h);
         }
         if (any_ball) {
@@ -2416,7 +2508,7 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
     }
     __syncthreads();
     if (ln < L && bl >= 0) {
-        const int b = ATTR ? b0 + bl * bs : b0 + bl;
+        const int b = (ATTR || JFR) ? b0 + bl * bs : b0 + bl;
         const SV vl = sv6(vs + 6 * ln);
         const Q4 ql = S.ql[ln];
         const V3 xl = S.xl[ln];
@@ -2469,6 +2561,28 @@ void mg_launch_env_step_crep(int maxl, int attr, int sens, int blocks, hipStream
         launch_crep<4, G16, false>(sens, blocks, s, P, A);
     }
 }
+#elif defined(MG_ENV_JFR_TU)
+// The joint-friction builds (mg_env_jfr.hip compiles this file with
+// MG_ENV_JFR_TU set): k_env_step for a coupled group whose
+// envs hold a friction DOF, k_artic_lanes for the uncoupled instances that do.
+// Force-reporting builds (dof_frc is always set here); friction together with
+// attractors, force sensors or contact reporting is refused by mg_simulate.
+void mg_launch_env_step_jfr(int maxl, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    if (maxl > 16)
+        MG_LAUNCH((k_env_step<MG_MAX_LINKS, 64, false, true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    else if (maxl > 4)
+        MG_LAUNCH((k_env_step<16, G16, false, true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A);
+    else
+        MG_LAUNCH((k_env_step<4, G16, false, true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A);
+}
+void mg_launch_artic_lanes_jfr(hipStream_t s, const MgStep& P, const MgArticArgs& A) {
+    if (A.nl > 16 || A.ndof > 16)
+        MG_LAUNCH((k_artic_lanes<MG_MAX_LINKS, 64, false, true, true>), dim3(A.na), dim3(64), 0, s, P, A);
+    else if (A.nl <= 4 && A.ndof <= 4)
+        MG_LAUNCH((k_artic_lanes<4, G16, false, true, true>), dim3((A.na + 3) / 4), dim3(64), 0, s, P, A);
+    else
+        MG_LAUNCH((k_artic_lanes<16, G16, false, true, true>), dim3((A.na + 3) / 4), dim3(64), 0, s, P, A);
+}
 #else
 // lanes per env / articulation: 16 (4 per wavefront) up to 16 links and 16
 // velocity slots; 64 (one per wavefront) up to MG_MAX_LINKS links and
@@ -2483,7 +2597,8 @@ static void launch_lanes(int blocks, hipStream_t s, const MgStep& P, const MgArt
 }
 template <int MAXL, int G, bool ATTR>
 static void launch_env_step(int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    if (A.crep) mg_launch_env_step_crep(MAXL, ATTR ? 1 : 0, A.ctorque ? 1 : 0, blocks, s, P, A);
+    if (A.jfr) mg_launch_env_step_jfr(MAXL, blocks, s, P, A);
+    else if (A.crep) mg_launch_env_step_crep(MAXL, ATTR ? 1 : 0, A.ctorque ? 1 : 0, blocks, s, P, A);
     else if (A.ctorque) mg_launch_env_step_sens(MAXL, ATTR ? 1 : 0, blocks, s, P, A);
     else if (A.dof_frc) MG_LAUNCH((k_env_step<MAXL, G, ATTR, true>), dim3(blocks), dim3(64), 0, s, P, A);
     else MG_LAUNCH((k_env_step<MAXL, G, ATTR, false>), dim3(blocks), dim3(64), 0, s, P, A);
@@ -2492,6 +2607,13 @@ static void launch_env_step(int blocks, hipStream_t s, const MgStep& P, const Mg
 hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
     if (!A.fixed_base || A.nl > MG_MAX_LINKS || A.ndof > MG_ENV_SLOTS_WIDE) return hipErrorNotSupported;
+    if (A.jfr) {
+        // instances that hold a friction DOF (migym_capi.cpp lists them apart),
+        // also of a group that steps in k_artic_chain otherwise
+        if (A.attr_idx || !A.dof_frc) return hipErrorNotSupported;
+        mg_launch_artic_lanes_jfr(s, P, A);
+        return hipGetLastError();
+    }
     if (A.attr_idx) {
         // instances that own an attractor (migym_capi.cpp lists them apart):
         // the attractor-aware build, also for a group that steps in

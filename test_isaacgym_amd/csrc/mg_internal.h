@@ -189,6 +189,10 @@ struct MgArticArgs {
     // over the frame's substeps; set while an actor reports DOF forces (the
     // force-reporting builds of the step kernels), else null
     float*       dof_frc;
+    // joint friction: 1 for the launch over the instances that
+    // hold a DOF with friction > 0 (k_artic_lanes' JFR build; dof_frc set, no
+    // attractors)
+    int          jfr;
 };
 
 // Coupled per-env step (mg_env.hip): MG_ENV_G lanes per env, one lane per
@@ -282,6 +286,10 @@ struct MgEnvArgs {
     int*         crep_n;      // [ne]
     const int*   crep_body;   // [nb]
     int          crep_stride;
+    // joint friction: 1 for a group whose envs hold a DOF with
+    // friction > 0 (k_env_step's JFR builds; dof_frc set, none of attr, ctorque,
+    // crep)
+    int          jfr;
 };
 
 // Force sensors (mg_sensor.hip). Lane = one sensor; the lanes
@@ -449,6 +457,9 @@ void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, cons
 // k_env_step's reporting builds (mg_env_crep.hip): sens: with the contact moment
 void mg_launch_env_step_crep(int maxl, int attr, int sens, int blocks, hipStream_t s, const MgStep& P,
                              const MgEnvArgs& A);
+// the joint-friction builds (mg_env_jfr.hip): k_env_step by maxl, k_artic_lanes by A's size
+void mg_launch_env_step_jfr(int maxl, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+void mg_launch_artic_lanes_jfr(hipStream_t s, const MgStep& P, const MgArticArgs& A);
 hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s);

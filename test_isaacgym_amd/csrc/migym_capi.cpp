@@ -80,6 +80,11 @@ struct ArticGroup {
     // step_offset .. of d_artic_split hold the other plain_count instances, then
     // these attr_count (k_artic_lanes' attractor-aware build)
     int attr_count = 0, plain_count = 0;
+    // stepped instances that hold a DOF with friction > 0 (jfr_route): rows
+    // step_offset .. of d_artic_jsplit hold the other jfr_plain instances, then
+    // these jfr_count (k_artic_lanes' joint-friction build); jfr_actor: the
+    // actor of the first of them, for a refusal's message
+    int jfr_count = 0, jfr_plain = 0, jfr_actor = -1;
 };
 
 // what steps a body, for an attractor on it (mg_set_attractors)
@@ -91,6 +96,9 @@ struct EnvGroup {
     int wide;            // 64 lanes per env (mg_env.hip k_env_step<32, 64>), else 16
     int max_free;        // most free bodies of one env of the group (velocity slots)
     int offset, count;   // rows of d_env
+    // an env of the group holds a DOF with friction > 0 (jfr_route): the group
+    // steps in k_env_step's joint-friction build; jfr_actor: that DOF's actor
+    int jfr = 0, jfr_actor = -1;
 };
 
 }  // namespace
@@ -262,6 +270,15 @@ struct mg_sim {
     bool attr_ev_pending = false, attr_dirty = false;
     int n_attr_free = 0, n_attr_env = 0;
     std::string attr_err;
+
+    // joint friction: the routing the DOF property table
+    // implies (jfr_route, at upload and at every mg_set_dof_props). Friction
+    // DOFs, instances in the lanes friction launches, envs of coupled friction
+    // groups; the uncoupled groups' split rows on the device and on the host;
+    // each row of d_env's first DOF
+    int jfr_ndof = 0, jfr_lanes = 0, jfr_envs = 0;
+    int* d_artic_jsplit = nullptr;        // [step rows][MG_ARTIC_I_N]
+    std::vector<int> h_jsplit, h_env_d0;
 
     // DOF force tensor (mg_enable_dof_forces): the step
     // kernels' rows [nd], then the per-DOF reporting flags [nd] the refresh
@@ -615,6 +632,7 @@ void mg_destroy_sim(mg_sim* s) {
     if (s->d_attr) (void)hipFree(s->d_attr);
     if (s->d_attr_idx) (void)hipFree(s->d_attr_idx);
     if (s->d_artic_split) (void)hipFree(s->d_artic_split);
+    if (s->d_artic_jsplit) (void)hipFree(s->d_artic_jsplit);
     delete s;
 }
 
@@ -671,6 +689,138 @@ static hipError_t chain_uni_upload(mg_sim* s) {
     for (size_t i = 0; i < s->groups.size(); ++i)
         std::memcpy(&u[i * MG_CHAIN_UNI_N], s->groups[i].uni, MG_CHAIN_UNI_N * sizeof(float));
     return hipMemcpy(s->d_chain_uni, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
+}
+
+// Joint friction routing of a DOF property table (global DOF
+// order, MG_DOFPROP_N per DOF, friction in field 9). Uncoupled instances that
+// hold a friction DOF step apart, in k_artic_lanes' joint-friction build (the
+// group's split rows: the plain instances, then these, as mg_set_attractors
+// lists attractor owners); a coupled group steps in k_env_step's joint-friction
+// build when any of its envs holds one. jfr_plan computes the routing and
+// changes nothing; jfr_commit installs it (fresh device rows) and cannot fail
+// after its allocation.
+struct JfrPlan {
+    int ndof = 0, lanes = 0, envs = 0;
+    std::vector<int> split;                    // empty: no lanes friction launch
+    std::vector<std::array<int, 3>> gc;        // per ArticGroup: plain, friction, actor
+    std::vector<std::array<int, 2>> ec;        // per EnvGroup: flag, actor
+    bool changed = false;
+};
+static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
+    const int nd = s->nd;
+    for (int d = 0; d < nd; ++d) {
+        const float f = props[(size_t)d * MG_DOFPROP_N + 9];
+        if (!(std::isfinite(f) && f >= 0.0f))
+            return fail(MG_ERR_ARG, "DOF %d: friction %g must be finite and non-negative", d, (double)f);
+        if (f > 0.0f) pl.ndof++;
+    }
+    auto fric_dof = [&](int d0, int n) {
+        for (int j = 0; j < n; ++j)
+            if (props[(size_t)(d0 + j) * MG_DOFPROP_N + 9] > 0.0f) return d0 + j;
+        return -1;
+    };
+    auto actor_of = [&](int d) {
+        const auto it = std::upper_bound(s->h_actor_dof.begin(), s->h_actor_dof.end(), d);
+        return (int)(it - s->h_actor_dof.begin()) - 1;
+    };
+    pl.gc.assign(s->groups.size(), {0, 0, -1});
+    std::vector<std::vector<char>> owns(s->groups.size());
+    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
+        const ArticGroup& g = s->groups[gi];
+        owns[gi].assign((size_t)g.step_count, 0);
+        for (int k = 0; pl.ndof > 0 && k < g.step_count; ++k) {
+            const int d = fric_dof(s->h_artic_step[(size_t)(g.step_offset + k) * MG_ARTIC_I_N + 1], g.ndof);
+            if (d < 0) continue;
+            owns[gi][k] = 1;
+            pl.lanes++;
+            if (pl.gc[gi][2] < 0) pl.gc[gi][2] = actor_of(d);
+        }
+    }
+    if (pl.lanes > 0) {
+        pl.split.resize(s->h_artic_step.size());
+        for (size_t gi = 0; gi < s->groups.size(); ++gi) {
+            const ArticGroup& g = s->groups[gi];
+            int* dst = pl.split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < g.step_count; ++k) {
+                    if ((owns[gi][k] != 0) != (pass == 1)) continue;
+                    std::memcpy(dst, s->h_artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
+                                MG_ARTIC_I_N * sizeof(int));
+                    dst += MG_ARTIC_I_N;
+                    pl.gc[gi][pass]++;
+                }
+        }
+    }
+    pl.ec.assign(s->env_groups.size(), {0, -1});
+    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) {
+        const EnvGroup& g = s->env_groups[gi];
+        if (g.tmpl < 0 || pl.ndof == 0) continue;
+        for (int r = g.offset; r < g.offset + g.count && !pl.ec[gi][0]; ++r) {
+            const int d = fric_dof(s->h_env_d0[r], g.ndof);
+            if (d >= 0) pl.ec[gi] = {1, actor_of(d)};
+        }
+        if (pl.ec[gi][0]) pl.envs += g.count;
+    }
+    pl.changed = pl.split != s->h_jsplit;
+    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) pl.changed = pl.changed || pl.ec[gi][0] != s->env_groups[gi].jfr;
+    return MG_OK;
+}
+static int jfr_commit(mg_sim* s, JfrPlan& pl) {
+    if (pl.changed) {
+        int* fresh = nullptr;
+        if (!pl.split.empty()) {
+            HIP_TRY(dalloc(&fresh, pl.split.size()));
+            if (hipMemcpy(fresh, pl.split.data(), pl.split.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(fresh);
+                return fail(MG_ERR_DEVICE, "joint friction routing: copy failed");
+            }
+        }
+        // no step may still read the rows this replaces
+        if (hipDeviceSynchronize() != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return fail(MG_ERR_DEVICE, "joint friction routing: device synchronize failed");
+        }
+        if (s->d_artic_jsplit) (void)hipFree(s->d_artic_jsplit);
+        s->d_artic_jsplit = fresh;
+        s->h_jsplit.swap(pl.split);
+    }
+    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
+        s->groups[gi].jfr_plain = pl.gc[gi][0];
+        s->groups[gi].jfr_count = pl.gc[gi][1];
+        s->groups[gi].jfr_actor = pl.gc[gi][2];
+    }
+    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) {
+        s->env_groups[gi].jfr = pl.ec[gi][0];
+        s->env_groups[gi].jfr_actor = pl.ec[gi][1];
+    }
+    s->jfr_ndof = pl.ndof;
+    s->jfr_lanes = pl.lanes;
+    s->jfr_envs = pl.envs;
+    return MG_OK;
+}
+// friction together with a feature whose joint-friction build does not exist
+// (attractors, force sensors, contact reporting on the same group): the
+// refusal mg_simulate reports, or 0
+static int jfr_refusal(const mg_sim* s) {
+    for (const ArticGroup& g : s->groups)
+        if (g.jfr_count > 0 && g.attr_count > 0)
+            return fail(MG_ERR_UNSUPPORTED, "actor %d: joint friction (DOF friction > 0) together with an attractor on an "
+                        "articulation of the same group is not built", g.jfr_actor);
+    for (const EnvGroup& g : s->env_groups) {
+        if (!g.jfr) continue;
+        const char* what = nullptr;
+        if (s->crep_on) what = "contact reporting";
+        else if (s->n_sens > 0 && s->sens_tmpl_env[g.tmpl]) what = "a force sensor";
+        else if (s->n_attr_env > 0)
+            for (const mg_attractor& a : s->attrs) {
+                const int ar = s->h_body_class[a.body] == ATTR_ENV_LINK ? s->h_body_artic[a.body] : -1;
+                if (ar >= 0 && s->h_artic_info[ar].tmpl == g.tmpl) what = "an attractor";
+            }
+        if (what)
+            return fail(MG_ERR_UNSUPPORTED, "actor %d: joint friction (DOF friction > 0) together with %s on the same "
+                        "coupled group is not built", g.jfr_actor, what);
+    }
+    return MG_OK;
 }
 
 int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
@@ -1195,6 +1345,8 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         if (g.count > 0) s->env_groups.push_back(g);
     }
     s->n_coupled = (int)env_rows.size();
+    s->h_env_d0.assign(env_rows.size(), 0);
+    for (size_t r = 0; r < env_rows.size(); ++r) s->h_env_d0[r] = env_flat[r * MG_ENV_I_N + 1];
     s->n_pile = (int)pile_rows.size();
     for (auto& r : pile_rows)
         for (int t = 0; t < r[4]; ++t) r[5 + t] = perm[r[5 + t]];
@@ -1394,6 +1546,11 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         if (g.uni_mass) chain_uni_dof(m->dof_props, g);
     HIP_TRY(dalloc(&s->d_chain_uni, std::max<size_t>(s->groups.size(), 1) * MG_CHAIN_UNI_N));
     HIP_TRY(chain_uni_upload(s));
+    if (nd > 0) {   // joint friction: which kernels step the DOFs with friction > 0
+        JfrPlan pl;
+        if (int rc_ = jfr_plan(s, m->dof_props, pl)) return rc_;
+        if (int rc_ = jfr_commit(s, pl)) return rc_;
+    }
     HIP_TRY(h2d(s->d_artic, artic_sorted.data(), artic_sorted.size() * sizeof(int)));
     HIP_TRY(h2d(s->d_artic_step, artic_step.data(), artic_step.size() * sizeof(int)));
     HIP_TRY(h2d(s->d_env, env_flat.data(), env_flat.size() * sizeof(int)));
@@ -1494,6 +1651,8 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // ignored; a changed table is sent here, in stream order before the step
     if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
     if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
+    if (s->jfr_ndof > 0)
+        if (int rc_ = jfr_refusal(s)) return rc_;
     if (s->attr_dirty) {
         if (s->capturing) return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
         HIP_TRY(hipMemcpyAsync(s->d_attr, s->h_attr, s->attrs.size() * MG_ATTR_N * sizeof(float),
@@ -1524,11 +1683,13 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     }
     const unsigned long long step_cid = capture_id(st);
     const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->step_out_ok &&
-                          s->attrs.empty() && !s->crep_on && (s->bind_root || s->bind_rb || s->bind_dof);
+                          s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 &&
+                          (s->bind_root || s->bind_rb || s->bind_dof);
     // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
     // write into the library's own buffer, so no caller-visible tensor changes
     float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && !s->crep_on && step_cid == 0;
+    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && !s->crep_on &&
+                          s->jfr_ndof == 0 && step_cid == 0;
     float* ho_root = host_out ? ho_base : nullptr;
     float* ho_rb = host_out ? ho_base + (size_t)s->na * MG_STATE_N : nullptr;
     float* ho_dof = host_out && s->nd ? ho_base + (size_t)(s->na + s->nb) * MG_STATE_N : nullptr;
@@ -1569,8 +1730,27 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.aff = 0;
             A.out_aff = 0;
         }
+        if (g.jfr_count > 0) {
+            // instances that hold a friction DOF step apart too (their own split
+            // rows; a group with both kinds of owner was refused above)
+            A.artic_i = s->d_artic_jsplit + (size_t)g.step_offset * MG_ARTIC_I_N;
+            A.na = g.jfr_plain;
+            A.aff = 0;
+            A.out_aff = 0;
+        }
         hipError_t e = mg_launch_artic_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "articulation step launch: %s", hipGetErrorString(e));
+        if (g.jfr_count > 0) {
+            MgArticArgs B = A;
+            B.artic_i = A.artic_i + (size_t)g.jfr_plain * MG_ARTIC_I_N;
+            B.na = g.jfr_count;
+            B.uni = nullptr;
+            B.jfr = 1;
+            B.dof_frc = s->d_dof_frc;   // the joint-friction build reports forces too
+            e = mg_launch_artic_step(P, B, st);
+            if (e != hipSuccess)
+                return fail(MG_ERR_DEVICE, "articulation step launch (joint friction): %s", hipGetErrorString(e));
+        }
         if (g.attr_count > 0) {
             MgArticArgs B = A;
             B.artic_i = A.artic_i + (size_t)g.plain_count * MG_ARTIC_I_N;
@@ -1626,6 +1806,14 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             // the contact-moment builds, which are force-reporting builds too
             // (rows of DOFs that do not report are masked by the refresh)
             A.ctorque = s->d_ctorque;
+            A.dof_frc = s->d_dof_frc;
+        }
+        if (g.jfr) {
+            // the joint-friction builds, force-reporting builds too; attractors,
+            // sensors and reporting on this group were refused above
+            A.jfr = 1;
+            A.attr_idx = nullptr;
+            A.attr = nullptr;
             A.dof_frc = s->d_dof_frc;
         }
         hipError_t e = mg_launch_env_step(P, A, st);
@@ -2040,7 +2228,16 @@ int32_t mg_discard_pending_sets(mg_sim* s) {
 }
 
 int32_t mg_step_out_supported(mg_sim* s) {
-    return s && s->uploaded && s->step_out_ok && s->attrs.empty() && !s->crep_on ? 1 : 0;
+    return s && s->uploaded && s->step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 ? 1 : 0;
+}
+
+int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (!out) return fail(MG_ERR_ARG, "null output");
+    out[0] = s->jfr_ndof;
+    out[1] = s->jfr_lanes;
+    out[2] = s->jfr_envs;
+    return MG_OK;
 }
 
 int32_t mg_last_set_deferred(mg_sim* s) { return s ? s->last_set_deferred : 0; }
@@ -2599,8 +2796,18 @@ int32_t mg_set_dof_props(mg_sim* s, const float* props_host) {
     if (s->nd == 0) return MG_OK;
     if (!props_host) return fail(MG_ERR_ARG, "null props");
     HIP_TRY(hipSetDevice(s->device));
+    // joint friction: the table decides which kernels a simulate launches (a
+    // graph captured before the call would replay the old launches); the new
+    // routing is built apart and committed after the table itself is copied
+    JfrPlan pl;
+    if (int rc_ = jfr_plan(s, props_host, pl)) return rc_;
+    if (pl.changed && s->capturing)
+        return fail(MG_ERR_STATE, "DOF friction changed which kernels step the DOFs after the step was captured into a "
+                    "graph (the replays keep the old launches); set it before the capture, or after an eager simulate");
     std::vector<float> dp = to_soa(props_host, s->nd, MG_DOFPROP_N);
+    if (pl.changed) HIP_TRY(hipDeviceSynchronize());   // the old launches read the old table to their end
     HIP_TRY(hipMemcpy(s->d_dof_props, dp.data(), dp.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc_ = jfr_commit(s, pl)) return rc_;
     for (ArticGroup& g : s->groups)
         if (g.uni_mass) chain_uni_dof(props_host, g);
     HIP_TRY(chain_uni_upload(s));

@@ -586,12 +586,24 @@ class Gym:
     def set_actor_dof_properties(self, env, handle, props):
         a = self._actor(env, handle)
         props = np.asarray(props)
+        if props.dtype.names and "friction" in props.dtype.names:
+            # the joint's Coulomb limit: a negative or
+            # non-finite one has no meaning, and nothing is changed
+            fr = np.asarray(props["friction"], dtype=np.float64)
+            if not np.all(np.isfinite(fr) & (fr >= 0.0)):
+                raise ValueError("set_actor_dof_properties: DOF friction must be finite and non-negative, got %r"
+                                 % (fr.tolist(),))
+        before = a.dof_props.copy()
         for f in DOF_PROPERTIES_DTYPE.names:
             if props.dtype.names and f in props.dtype.names:
                 a.dof_props[f] = props[f]
         sim = env.sim
         if sim.finalized and sim.native:
-            self._push_dof_props(sim)
+            try:
+                self._push_dof_props(sim)
+            except N.MigymError:
+                a.dof_props[...] = before      # a refused table (mg_set_dof_props) leaves the actor's as it was
+                raise
         return True
 
     def _push_dof_props(self, sim):
