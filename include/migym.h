@@ -182,6 +182,7 @@ typedef struct mg_sim mg_sim;
 /* ---- library / device ---------------------------------------------------- */
 int32_t     mg_abi_version(void);
 const char* mg_last_error(void);
+int32_t     mg_last_error_code(void);   /* the MG_ERR_* of that message (for entries that return NULL) */
 int32_t     mg_device_count(void);           /* HIP devices visible; 0 on a host without a GPU */
 
 /* ---- sim lifetime ---------------------------------------------------------
@@ -608,6 +609,37 @@ int32_t     mg_debug_copy_env_ctab(mg_sim* sim, int32_t k, float* dst, int32_t c
  * possible for the sim. Returns the number of groups, < 0 on error. */
 #define MG_DEBUG_GROUP_N 8
 int32_t     mg_debug_artic_groups(mg_sim* sim, int32_t* out, int32_t cap);
+/* Diagnostics: the layout plan mg_upload_model would commit for a model (the
+ * storage order, launch groups and index tables it derives on the host), with
+ * no sim and no device: the call touches no GPU. NULL + mg_last_error() when
+ * the model is refused, with mg_upload_model's message. mg_debug_layout_table
+ * points *data at table `which` (owned by the plan, valid until it is freed)
+ * and sets *count to its elements: int32, except PILE_PAIRS (uint32) and
+ * CENV_CTAB_OFF (int64). SCALARS: MG_LAYOUT_HEAD_N ints — bodies, actors,
+ * DOFs, nf, nf1, nf_rigid, coupled envs, pile envs, max_actor_dofs, roots_free,
+ * step_out_ok, articulation groups, env groups — then MG_LAYOUT_GROUP_N per
+ * articulation group (chain, aff, aff_b0, aff_d0, aff_ds, out_aff, out_g0,
+ * out_r0, offset, count, step_offset, step_count, uni_mass, links), then
+ * MG_LAYOUT_ENVGROUP_N per env group (template, wide, max_free, offset, count). */
+typedef struct mg_layout mg_layout;
+#define MG_LAYOUT_SCALARS       0
+#define MG_LAYOUT_PERM          1   /* global body -> storage slot */
+#define MG_LAYOUT_ARTIC_SORTED  2
+#define MG_LAYOUT_ARTIC_STEP    3
+#define MG_LAYOUT_ENV_FLAT      4   /* coupled env rows, by group */
+#define MG_LAYOUT_PAIRS         5
+#define MG_LAYOUT_PILE_ROWS     6
+#define MG_LAYOUT_PILE_BODY     7
+#define MG_LAYOUT_PILE_SLOTS    8
+#define MG_LAYOUT_PILE_PAIRS    9
+#define MG_LAYOUT_CENV_ROW      10  /* coupled env k (env order) -> its row of ENV_FLAT */
+#define MG_LAYOUT_CENV_CTAB_OFF 11  /* ... -> float offset of its contact-table record */
+#define MG_LAYOUT_HEAD_N        13
+#define MG_LAYOUT_GROUP_N       14
+#define MG_LAYOUT_ENVGROUP_N    5
+mg_layout*  mg_debug_plan_layout(const mg_sim_params* params, const mg_model* model);
+int32_t     mg_debug_layout_table(const mg_layout* layout, int32_t which, const void** data, int64_t* count);
+void        mg_debug_free_layout(mg_layout* layout);
 int         mg_env_ctab_floats(void);
 int         mg_env_carry_floats(void);
 /* Number of bodies advanced by the free-body kernel / articulations by the

@@ -28,6 +28,11 @@ MG_LINK_F_N = 16
 MG_LINK_I_N = 4
 MG_ARTIC_I_N = 4
 MG_DEBUG_GROUP_N = 8       # include/migym.h mg_debug_artic_groups
+# mg_debug_layout_table (include/migym.h): table ids, scalar block strides
+(MG_LAYOUT_SCALARS, MG_LAYOUT_PERM, MG_LAYOUT_ARTIC_SORTED, MG_LAYOUT_ARTIC_STEP, MG_LAYOUT_ENV_FLAT,
+ MG_LAYOUT_PAIRS, MG_LAYOUT_PILE_ROWS, MG_LAYOUT_PILE_BODY, MG_LAYOUT_PILE_SLOTS, MG_LAYOUT_PILE_PAIRS,
+ MG_LAYOUT_CENV_ROW, MG_LAYOUT_CENV_CTAB_OFF) = range(12)
+MG_LAYOUT_HEAD_N, MG_LAYOUT_GROUP_N, MG_LAYOUT_ENVGROUP_N = 13, 14, 5
 MG_ATMPL_I_N = 4
 MG_ACOLL_N = 4
 
@@ -151,6 +156,7 @@ def _load():
     sig = {
         "mg_abi_version": (i32, []),
         "mg_last_error": (ctypes.c_char_p, []),
+        "mg_last_error_code": (i32, []),
         "mg_device_count": (i32, []),
         "mg_create_sim": (vp, [i32, ctypes.POINTER(MgSimParams)]),
         "mg_destroy_sim": (None, [vp]),
@@ -212,6 +218,9 @@ def _load():
         "mg_contact_reporting": (i32, [vp]),
         "mg_refresh_rigid_contacts": (i32, [vp, vp, i32, i32, vp, vp]),
         "mg_joint_friction_stats": (i32, [vp, vp]),
+        "mg_debug_plan_layout": (vp, [ctypes.POINTER(MgSimParams), ctypes.POINTER(MgModel)]),
+        "mg_debug_layout_table": (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]),
+        "mg_debug_free_layout": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -242,6 +251,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_force_sensors", "mg_refresh_force_sensor", "mg_num_force_sensors",
     "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
     "mg_joint_friction_stats",
+    "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
 )
 
 
@@ -257,6 +267,25 @@ def last_error():
 def check(rc, what):
     if rc != MG_OK:
         raise MigymError("%s failed (%d): %s" % (what, rc, last_error()))
+
+
+def plan_layout(params, model):
+    """The layout plan of a model (mg_debug_plan_layout; no GPU): {table id: numpy array}, or
+    MigymError with the library's refusal."""
+    h = lib.mg_debug_plan_layout(ctypes.byref(params), ctypes.byref(model))
+    if not h:
+        raise MigymError(last_error())
+    try:
+        out = {}
+        for which in range(12):
+            data, n = ctypes.c_void_p(), ctypes.c_int64()
+            check(lib.mg_debug_layout_table(h, which, ctypes.byref(data), ctypes.byref(n)), "mg_debug_layout_table")
+            dt = {MG_LAYOUT_PILE_PAIRS: np.uint32, MG_LAYOUT_CENV_CTAB_OFF: np.int64}.get(which, np.int32)
+            buf = ctypes.string_at(data.value, n.value * np.dtype(dt).itemsize) if n.value else b""
+            out[which] = np.frombuffer(buf, dt).copy()
+        return out
+    finally:
+        lib.mg_debug_free_layout(h)
 
 
 def device_count():

@@ -17,12 +17,14 @@
 #include "mg_internal.h"
 #include "mg_chainlink.h"
 #include "mg_attractor.h"
+#include "mg_layout.h"
 
 thread_local MgKernelTimer* mg_timer = nullptr;
 
 namespace {
 
 thread_local std::string g_err;
+thread_local int g_err_code = MG_OK;   // of g_err (mg_last_error_code)
 
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail(int code, const char* fmt, ...) {
@@ -32,6 +34,7 @@ int fail(int code, const char* fmt, ...) {
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
     g_err = buf;
+    g_err_code = code;
     return code;
 }
 
@@ -42,12 +45,54 @@ int fail(int code, const char* fmt, ...) {
             return fail(MG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// Owner of one allocation released by Free: move-only, frees on destruction or
+// when assigned over, converts to T* where the raw pointer is used.
+template <class T, hipError_t (*Free)(void*)>
+struct Owned {
+    T* p = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() {
+        if (p) (void)Free(p);
+        p = nullptr;
+    }
+    operator T*() const { return p; }
+};
+// device memory; alloc() replaces what it held, with max(n, 1) elements
 template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc((void**)p, n * sizeof(T));
-}
+struct DevBuf : Owned<T, hipFree> {
+    hipError_t alloc(size_t n) {
+        this->reset();
+        return hipMalloc((void**)&this->p, std::max<size_t>(n, 1) * sizeof(T));
+    }
+    hipError_t zero(size_t n) {    // alloc + clear
+        hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemset(this->p, 0, std::max<size_t>(n, 1) * sizeof(T));
+    }
+    hipError_t upload(const T* h, size_t n, size_t room = 0) {   // alloc max(n, room) + copy n
+        hipError_t e = alloc(std::max(n, room));
+        return e != hipSuccess || n == 0 || !h ? e : hipMemcpy(this->p, h, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t upload(const std::vector<T>& h, size_t room = 0) { return upload(h.data(), h.size(), room); }
+};
+// page-locked host memory; mapped: for hipHostGetDevicePointer
+template <class T>
+struct HostBuf : Owned<T, hipHostFree> {
+    hipError_t alloc(size_t n, bool mapped) {
+        this->reset();
+        return hipHostMalloc((void**)&this->p, n * sizeof(T),
+                             mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault);
+    }
+};
 
 // host AoS [n][ncol] -> device SoA [ncol][n]
 template <class T>
@@ -58,24 +103,15 @@ std::vector<T> to_soa(const T* aos, int n, int ncol) {
     return soa;
 }
 
-struct ArticGroup {
-    int chain;                     // serial chain with one DOF per moving link (MgArticArgs.chain)
-    // k_artic_chain's shared constants (mg_chainlink.h): the stepped instances'
-    // global first body / first DOF, whether their link mass rows and gravity
-    // flags agree (set at upload), whether their DOF properties agree (upload
-    // and mg_set_dof_props), the constants themselves
-    std::vector<int> step_body0, step_dof0;
-    bool uni_mass = false, uni_dof = false;
+// an articulation group (mg_layout.h) with what later calls add to it
+struct ArticGroup : MgArticGroup {
+    ArticGroup() = default;
+    explicit ArticGroup(MgArticGroup&& g) : MgArticGroup(std::move(g)) {}
+    // k_artic_chain's shared constants (mg_chainlink.h): whether the stepped
+    // instances' DOF properties agree (upload and mg_set_dof_props), the
+    // constants themselves
+    bool uni_dof = false;
     float uni[MG_CHAIN_UNI_N] = {};
-    int tmpl, first_link, nl, ndof, fixed_base;
-    int nbody;                     // bodies per instance (nl minus the virtual links of ball joints)
-    int offset, count;             // into the template-sorted instance list (all instances)
-    int step_offset, step_count;   // into the list stepped by k_artic_chain / k_artic_lanes (uncoupled envs)
-    // the stepped instances' rows are affine in the instance (MgArticArgs::aff),
-    // and so are their fused-refresh rows (out_aff: rigid-body row og0 + a nl +
-    // l, actor row or0 + a)
-    int aff = 0, aff_b0 = 0, aff_d0 = 0, aff_ds = 0;
-    int out_aff = 0, out_g0 = 0, out_r0 = 0;
     // stepped instances that own an attractor (mg_set_attractors): rows
     // step_offset .. of d_artic_split hold the other plain_count instances, then
     // these attr_count (k_artic_lanes' attractor-aware build)
@@ -87,58 +123,129 @@ struct ArticGroup {
     int jfr_count = 0, jfr_plain = 0, jfr_actor = -1;
 };
 
-// what steps a body, for an attractor on it (mg_set_attractors)
-enum AttrClass : char { ATTR_NONE = 0, ATTR_FREE, ATTR_LINK, ATTR_ENV_LINK, ATTR_ENV_FREE, ATTR_PILE };
-
-// coupled envs (mg_env.hip) of one articulation template (tmpl -1: none)
-struct EnvGroup {
-    int tmpl, first_link, nl, ndof, floating;
-    int wide;            // 64 lanes per env (mg_env.hip k_env_step<32, 64>), else 16
-    int max_free;        // most free bodies of one env of the group (velocity slots)
-    int offset, count;   // rows of d_env
+// a coupled env group (mg_layout.h)
+struct EnvGroup : MgEnvGroup {
+    explicit EnvGroup(const MgEnvGroup& g) : MgEnvGroup(g) {}
     // an env of the group holds a DOF with friction > 0 (jfr_route): the group
     // steps in k_env_step's joint-friction build; jfr_actor: that DOF's actor
     int jfr = 0, jfr_actor = -1;
 };
 
-}  // namespace
+static_assert(sizeof(MgSlotRec) == sizeof(std::array<int, 4>), "MgLayout::slot_rec is uploaded as MgSlotRec");
+// the device headers' constants the planner needs
+MgLayoutSizes layout_sizes() {
+    return {MG_MAX_LINKS, MG_MAX_DOFS,
+            MG_ENV_I_N, MG_ENV_MAXF, MG_ENV_MAXS, MG_ENV_SLOTS_WIDE, MG_ENV_FREE0, MG_ENV_STATIC0,
+            MG_PILE_I_N, MG_PILE_MAXB, MG_PILE_ST0, MG_PILE_MAXPAIRS, MG_PILE_MAXSH, MG_PILE_GROUND,
+            MG_TREC_N, MG_TREC_MASS, MG_OBB_N,
+            mg_env_ctab_floats(), {mg_env_ctab_record_floats(0), mg_env_ctab_record_floats(1)}};
+}
 
-struct mg_sim {
-    int device = 0;
-    mg_sim_params params{};
-    bool uploaded = false;
-
-    int nenv = 0, na = 0, nb = 0, nd = 0, ntb = 0, ns = 0, nf = 0, nartic = 0, ntl = 0;
-    int max_actor_dofs = 0;
-    int nf1 = 0;   // single-shape free bodies (storage slots 0..nf1-1)
-    int nf_rigid = 0;   // free bodies of uncoupled envs (slots 0..nf_rigid-1), free-body kernel
-
-    float* d_state = nullptr;     // [13][nb]
-    float* d_mass = nullptr;      // [12][nb]
+// The device buffers mg_upload_model fills from the layout plan, committed to
+// the sim as one (mg_sim derives from it: s->d_state).
+struct ModelBufs {
+    DevBuf<float> d_state;     // [13][nb]
+    DevBuf<float> d_mass;      // [12][nb]
     // Bodies are stored in an internal order (free bodies first, by launch group
     // and template; then each articulation's links contiguously; then the rest)
     // so every kernel's lanes touch contiguous SoA slots. Tensors stay in the
     // global (Isaac Gym) order: the gather / scatter index maps fold in `perm`.
-    int* d_body_tmpl = nullptr;   // [nb] internal order
-    int* d_free_global = nullptr; // [nf] global ids of the free bodies (internal 0..nf-1)
-    int* d_perm = nullptr;        // [nb] global body -> internal slot
-    float* d_tbf = nullptr;
-    float* d_trec = nullptr;      // [ntb][MG_TREC_N] compact template records (k_rigid_step1)
-    int* d_tbi = nullptr;
-    float* d_shapes = nullptr;
-    float* d_hulls = nullptr;     // convex hull records (MG_SHAPE_CONVEX)
-    float* d_shape_obb = nullptr; // [ns][MG_OBB_N] shape-frame boxes (coupled step's pair screen)
-    int* d_actor_root = nullptr;  // [na] internal slot of each actor's root body
-    int* d_body_actor = nullptr;  // [nb] global body -> the actor it is the root of, or -1
+    DevBuf<int> d_body_tmpl;   // [nb] internal order
+    DevBuf<int> d_free_global; // [nf] global ids of the free bodies (internal 0..nf-1)
+    DevBuf<int> d_perm;        // [nb] global body -> internal slot
+    DevBuf<float> d_tbf;
+    DevBuf<float> d_trec;      // [ntb][MG_TREC_N] compact template records (k_rigid_step1)
+    DevBuf<int> d_tbi;
+    DevBuf<float> d_shapes;
+    DevBuf<float> d_hulls;     // convex hull records (MG_SHAPE_CONVEX)
+    DevBuf<float> d_shape_obb; // [ns][MG_OBB_N] shape-frame boxes (coupled step's pair screen)
+    DevBuf<int> d_actor_root;  // [na] internal slot of each actor's root body
+    DevBuf<int> d_body_actor;  // [nb] global body -> the actor it is the root of, or -1
+    DevBuf<int> d_root_row;    // [nb] internal slot -> actor row, -1 for non-roots (fused root sets)
+    DevBuf<int> d_slot_global; // [nb] internal slot -> global body (rigid-body tensor row)
+    DevBuf<int> d_slot_actor;  // [nb] internal slot -> actor row it is the root of, or -1
+    DevBuf<MgSlotRec> d_slot_rec;   // [nb] {d_root_row, d_body_tmpl, d_slot_global, d_slot_actor} of each slot
+    DevBuf<int> d_actor_dof;   // [na+1]
+    DevBuf<float> d_cforce;    // [3][nb]
+    DevBuf<float> d_ext;       // [6][nb]
+    DevBuf<float> d_dof;       // [2][nd]: pos, vel
+    DevBuf<float> d_dof_tgt;   // [3][nd]: target pos, target vel, actuation force
+    DevBuf<float> d_dof_props; // [12][nd]
+    DevBuf<float> d_dof_frc;   // [2][nd] DOF force tensor (mg_enable_dof_forces)
+    DevBuf<int> d_artic;       // [nartic][4] sorted by template
+    DevBuf<float> d_link_f;
+    DevBuf<int> d_link_i;
+    DevBuf<int> d_artic_step;  // [..][4] instances stepped by k_artic_chain / k_artic_lanes
+    DevBuf<int> d_artic_jsplit;   // [step rows][MG_ARTIC_I_N] joint friction's split rows (jfr_commit)
+    DevBuf<int> d_env;         // [n_coupled][MG_ENV_I_N] coupled envs, by group
+    DevBuf<int> d_pairs;       // [..][4] candidate shape pairs of the coupled envs
+    DevBuf<float> d_fpatch;    // [pairs][MG_FP_N] friction patch records (coupled step, persistent)
+    DevBuf<float> d_gpatch;    // [MG_FP_N][nf1] ground patches of the single-shape free bodies (persistent)
+    DevBuf<float> d_chain_uni; // [groups][MG_CHAIN_UNI_N] shared constants of chain groups (ArticGroup.uni)
+    DevBuf<unsigned> d_fp_mask;   // [n_coupled][MG_FP_W] pairs holding a patch
+    DevBuf<float> d_env_carry;    // [n_coupled][mg_env_carry_floats] coupled step state between substep launches
+    DevBuf<float> d_env_ctab;     // [n_coupled][mg_env_ctab_floats] contacts of one substep (k_env_np -> k_env_step)
+    // free-body piles (mg_pile.hip): coupled envs of more than MG_ENV_MAXF free
+    // bodies and no articulation, one wavefront each
+    DevBuf<int> d_pile_i;      // [n_pile][MG_PILE_I_N]
+    DevBuf<int> d_pile_body;   // their free bodies' internal slots
+    DevBuf<unsigned> d_pile_pairs;  // packed candidate pairs (local shape slots, mg_internal.h)
+    DevBuf<int> d_pile_slots;  // [..][2] local shape slots: participant, shape
+};
+
+// What mg_upload_model builds apart and commits to the sim as one: the plan
+// (mg_layout.h: counts, storage order, index tables and the host mirrors later
+// calls read), its device buffers, and the groups. The plan's group lists move
+// into `groups` / `env_groups`, which carry what later calls add.
+struct Model : ModelBufs {
+    MgLayout layout;
+    std::vector<ArticGroup> groups;
+    std::vector<EnvGroup> env_groups;
+    // joint friction's routing (jfr_commit): friction DOFs, instances in the
+    // lanes friction launches, envs of coupled friction groups; the host copy
+    // of d_artic_jsplit
+    int jfr_ndof = 0, jfr_lanes = 0, jfr_envs = 0;
+    std::vector<int> h_jsplit;
+};
+// the device form of the force sensor table (mg_set_force_sensors, MgSensorArgs)
+struct SensBufs {
+    DevBuf<int> d_sens_i;
+    DevBuf<float> d_sens_f;
+    DevBuf<int> d_sart_i;
+    DevBuf<int> d_sens_flag;           // mark [n_sart], valid [n_sart], parity [1]
+    DevBuf<float> d_sens_hist;
+    DevBuf<float> d_sens_save;
+    DevBuf<float> d_sens_out;          // [n_sens][6]
+};
+// the rigid contact list's staging and output (mg_set_contact_reporting)
+struct CrepBufs {
+    DevBuf<float> d_crep_cenv;         // [2 MG_ENV_MAXCT_WIDE][MG_CREP_N][n_coupled], column = row of d_env
+    DevBuf<int> d_crep_cenv_n;         // [n_coupled]
+    DevBuf<int> d_crep_col;            // [n_coupled] coupled env k -> its column
+    DevBuf<float> d_crep_pile;         // [MG_PILE_MAXPT][MG_CREP_N][n_pile]
+    DevBuf<int> d_crep_pile_n;         // [n_pile]
+    DevBuf<float> d_crep_free;         // [MG_CREP_FREE_CAP][MG_CREP_N][nf_rigid]
+    DevBuf<int> d_crep_free_n;         // [nf_rigid]
+    DevBuf<int> d_crep_env;            // [owners] owner -> env
+    DevBuf<int> d_crep_blk;            // [blocks] pass 1 -> pass 2
+    DevBuf<mg_rigid_contact> d_crep_out;
+    DevBuf<int> d_crep_hdr;            // [2]
+};
+
+}  // namespace
+
+struct mg_sim : Model, SensBufs, CrepBufs {
+    int device = 0;
+    mg_sim_params params{};
+    bool uploaded = false;
+
     // Step fusion (mg_set_fusion): a device-resident, non-indexed root-state set
-    // of a sim whose actor roots are all single-shape free bodies is read by the
-    // next simulate's free-body kernel (d_root_row: internal slot -> actor row,
-    // -1 for non-roots) instead of a scatter launch; any earlier reader of the
+    // of a sim whose actor roots are all single-shape free bodies
+    // (layout.roots_free) is read by the next simulate's free-body kernel
+    // (d_root_row) instead of a scatter launch; any earlier reader of the
     // state flushes it as the scatter. A root refresh into the bound root tensor
     // also gathers the bound rigid-body tensor (one launch), and the rigid-body
     // refresh that follows is served by it while the state is unchanged.
-    int* d_root_row = nullptr;
-    bool roots_free = false;
     int fusion = 0;   // opt-in (mg_set_fusion): Isaac Gym copies at set time and refreshes exactly what is asked
     const float* pend_root = nullptr;
     const float* pend_tgt[3] = {nullptr, nullptr, nullptr};   // fused DOF target sets (pos, vel, force)
@@ -152,51 +259,14 @@ struct mg_sim {
     long long state_gen = 0, rb_gen = -1, out_gen = -1;   // out_gen: bound tensors written by the step
     unsigned long long out_cap = 0;
     // DOF state generation (simulate, mg_set_dof_state) and the one the step
-    // wrote into the bound DOF tensor (MG_FUSE_STEP_OUT)
+    // wrote into the bound DOF tensor (MG_FUSE_STEP_OUT; layout.step_out_ok:
+    // it covers the sim)
     long long dof_sgen = 0, dof_gen = -1;
     unsigned long long dof_cap = 0;
-    // MG_FUSE_STEP_OUT covers the sim: every body is stepped by a kernel that
-    // writes its rows (single-shape free bodies in k_rigid_step1, links of
-    // uncoupled serial chains in k_artic_chain), so the refreshes after a
-    // simulate can be served by the step itself
-    bool step_out_ok = false;
-    int* d_slot_global = nullptr; // [nb] internal slot -> global body (rigid-body tensor row)
-    int* d_slot_actor = nullptr;  // [nb] internal slot -> actor row it is the root of, or -1
-    MgSlotRec* d_slot_rec = nullptr;   // [nb] {d_root_row, d_body_tmpl, d_slot_global, d_slot_actor} of each slot
     int last_set_deferred = 0;    // the last mg_set_* left its source to be read by the next simulate
-    int* d_actor_dof = nullptr;   // [na+1]
-    float* d_cforce = nullptr;    // [3][nb]
-    float* d_ext = nullptr;       // [6][nb]
     bool ext_pending = false;
 
-    float* d_dof = nullptr;       // [2][nd]: pos, vel
-    float* d_dof_tgt = nullptr;   // [3][nd]: target pos, target vel, actuation force
-    float* d_dof_props = nullptr; // [12][nd]
-    int* d_artic = nullptr;       // [nartic][4] sorted by template
-    float* d_link_f = nullptr;
-    int* d_link_i = nullptr;
-    std::vector<ArticGroup> groups;
-    int* d_artic_step = nullptr;  // [..][4] instances stepped by k_artic_chain / k_artic_lanes
-    int* d_env = nullptr;         // [n_coupled][MG_ENV_I_N] coupled envs, by group
-    int* d_pairs = nullptr;       // [..][4] candidate shape pairs of the coupled envs
-    float* d_fpatch = nullptr;    // [pairs][MG_FP_N] friction patch records (coupled step, persistent)
-    float* d_gpatch = nullptr;    // [MG_FP_N][nf1] ground patches of the single-shape free bodies (persistent)
-    float* d_chain_uni = nullptr; // [groups][MG_CHAIN_UNI_N] shared constants of chain groups (ArticGroup.uni)
-    unsigned* d_fp_mask = nullptr;   // [n_coupled][MG_FP_W] pairs holding a patch
-    float* d_env_carry = nullptr;    // [n_coupled][mg_env_carry_floats] coupled step state between substep launches
-    int nhull_floats = 0;            // floats of the hull table (k_env_np stages it in LDS when small)
-    float* d_env_ctab = nullptr;     // [n_coupled][mg_env_ctab_floats] contacts of one substep (k_env_np -> k_env_step)
-    int n_coupled = 0;
-    std::vector<EnvGroup> env_groups;
-    // free-body piles (mg_pile.hip): coupled envs of more than MG_ENV_MAXF free
-    // bodies and no articulation, one wavefront each
-    int n_pile = 0;
-    int* d_pile_i = nullptr;      // [n_pile][MG_PILE_I_N]
-    int* d_pile_body = nullptr;   // their free bodies' internal slots
-    unsigned* d_pile_pairs = nullptr;  // packed candidate pairs (local shape slots, mg_internal.h)
-    int* d_pile_slots = nullptr;  // [..][2] local shape slots: participant, shape
-
-    float* d_stage = nullptr;     // host-transfer staging (floats)
+    DevBuf<float> d_stage;     // host-transfer staging (floats)
     size_t stage_n = 0;
     // CPU pipeline (host state tensors): a full host root set is read by the next
     // step kernel (no scatter launch; h_root_in below); and from the
@@ -208,11 +278,11 @@ struct mg_sim {
     // sent in stream order), so the caller may overwrite its tensor right away —
     // Isaac Gym's copy-at-set — even though the transfer itself is asynchronous;
     // pin_ev: the last transfer out of it (waited on before it is refilled)
-    char* h_pin = nullptr;
+    HostBuf<char> h_pin;
     size_t h_pin_n = 0;
     hipEvent_t pin_ev = nullptr;
     bool pin_ev_pending = false;
-    float* d_host_out = nullptr;
+    DevBuf<float> d_host_out;
     size_t host_out_n = 0;
     // zero-copy variants (mg_host_stage): the host stage itself, page-locked and
     // mapped into the device's address space — the step kernels write their rows
@@ -221,29 +291,27 @@ struct mg_sim {
     // (root_ev: its last reader, waited on before it is refilled)
     bool has_light = false;           // mg_set_light (else the default light)
     mg_light light{};
-    float* h_stage = nullptr;
+    HostBuf<float> h_stage;
     float* d_stage_alias = nullptr;
     size_t h_stage_n = 0;
-    float* h_root_in = nullptr;
+    HostBuf<float> h_root_in;
     float* d_root_in_alias = nullptr;
     hipEvent_t root_ev = nullptr;
     bool root_ev_pending = false;
     bool ho_alias = false;            // the last fetch staged into h_stage: the step writes there
     const float* ho_written = nullptr;   // the stage the last simulate wrote (ho_*_gen refer to it)
     long long ho_root_gen = -1, ho_rb_gen = -1, ho_dof_gen = -1;
-    int* d_stage_idx = nullptr;
+    DevBuf<int> d_stage_idx;
     size_t stage_idx_n = 0;
 
-    // host copies kept for the camera renderer's shape lists
-    std::vector<int> h_perm, h_body_tmpl, h_tbi;
     // camera render (mg_render.hip)
-    float* d_rstate = nullptr;    // [13][nb] pose snapshot of render_all_camera_sensors
+    DevBuf<float> d_rstate;    // [13][nb] pose snapshot of render_all_camera_sensors
     bool rstate_valid = false;
-    MgRShape* d_rshapes = nullptr;
-    int* d_env_shape_first = nullptr;
+    DevBuf<MgRShape> d_rshapes;
+    DevBuf<int> d_env_shape_first;
     int n_rshapes = 0;
     bool render_ready = false;
-    MgRenderCam* d_cams = nullptr;
+    DevBuf<MgRenderCam> d_cams;
     int cam_cap = 0;
     std::vector<mg_camera> cam_host;      // last uploaded table (as given)
     std::vector<MgRenderCam> cam_dev;     // its device form
@@ -259,13 +327,10 @@ struct mg_sim {
     // the group's plain rows, then its attractor rows), the counts on free
     // bodies and coupled envs' links, and the refusal mg_simulate reports
     std::vector<mg_attractor> attrs;
-    std::vector<char> h_body_class;       // global body -> AttrClass
-    std::vector<int> h_body_grp, h_body_inst;   // a stepped articulation's link: group, stepped instance
-    std::vector<int> h_artic_step;        // host copy of d_artic_step
-    float* d_attr = nullptr;
-    int* d_attr_idx = nullptr;            // [nb]
-    int* d_artic_split = nullptr;         // [step rows][MG_ARTIC_I_N]
-    float* h_attr = nullptr;
+    DevBuf<float> d_attr;
+    DevBuf<int> d_attr_idx;            // [nb]
+    DevBuf<int> d_artic_split;         // [step rows][MG_ARTIC_I_N]
+    HostBuf<float> h_attr;
     hipEvent_t attr_ev = nullptr;
     bool attr_ev_pending = false, attr_dirty = false;
     int n_attr_free = 0, n_attr_env = 0;
@@ -274,67 +339,36 @@ struct mg_sim {
     // joint friction: the routing the DOF property table
     // implies (jfr_route, at upload and at every mg_set_dof_props). Friction
     // DOFs, instances in the lanes friction launches, envs of coupled friction
-    // groups; the uncoupled groups' split rows on the device and on the host;
-    // each row of d_env's first DOF
-    int jfr_ndof = 0, jfr_lanes = 0, jfr_envs = 0;
-    int* d_artic_jsplit = nullptr;        // [step rows][MG_ARTIC_I_N]
-    std::vector<int> h_jsplit, h_env_d0;
+    // groups; the uncoupled groups' split rows on the device (d_artic_jsplit)
+    // and on the host
+    // (Model::jfr_*, h_jsplit)
 
     // DOF force tensor (mg_enable_dof_forces): the step
     // kernels' rows [nd], then the per-DOF reporting flags [nd] the refresh
     // applies; the force-reporting builds step while dof_frc_n > 0
-    float* d_dof_frc = nullptr;           // [2][nd]
-    std::vector<int> h_actor_dof;         // [na + 1]
     int dof_frc_n = 0;                    // DOFs of the actors that report
 
-    // force sensors (mg_set_force_sensors, mg_sensor.hip). Host
-    // facts kept at upload: every articulation's first global body, first DOF,
-    // template and whether it steps in a coupled env; global body -> its
-    // articulation (-1: a single-body actor); the template tables. The table as
-    // given and its device form (MgSensorArgs), allocated by the first table
+    // force sensors (mg_set_force_sensors, mg_sensor.hip). The
+    // table as given and its device form (SensBufs), allocated by the first table
     // with a sensor; sens_tmpl_env: templates whose coupled instances carry a
     // sensor (their env groups step in k_env_step's contact-moment builds);
     // sens_err: the refusal mg_simulate reports.
-    struct ArticInfo { int g0, d0, tmpl, coupled; };
-    std::vector<ArticInfo> h_artic_info;
-    std::vector<int> h_body_artic, h_link_i, h_atmpl;
     std::vector<mg_force_sensor> sensors;
     std::vector<char> sens_tmpl_env;
     std::string sens_err;
     int n_sens = 0, n_sart = 0, sens_nhb = 0;
-    int* d_sens_i = nullptr;
-    float* d_sens_f = nullptr;
-    int* d_sart_i = nullptr;
-    int* d_sens_flag = nullptr;           // mark [n_sart], valid [n_sart], parity [1]
-    float* d_sens_hist = nullptr;
-    float* d_sens_save = nullptr;
-    float* d_sens_out = nullptr;          // [n_sens][6]
-    float* d_ctorque = nullptr;           // [3][nb], allocated with the first sensor table
+    DevBuf<float> d_ctorque;           // [3][nb], allocated with the first sensor table
 
     // rigid contact list (mg_set_contact_reporting, mg_contact.hip, DESIGN.md
     // §3.14). While crep_on the reporting builds of the step kernels fill the
     // staging records and k_contact_compact packs them into d_crep_out; the
-    // buffers are allocated by the call that turns reporting on. crep_valid: a
+    // buffers (CrepBufs) are allocated by the call that turns reporting on. crep_valid: a
     // reporting simulate has run since. The header (true total, stored total)
     // is kept on the device and in mapped host memory, which the refresh reads
     // after waiting for the stream.
     bool crep_on = false, crep_valid = false;
     int crep_capacity = 0;
-    std::vector<int> h_slot_env;          // [nb] internal slot of an actor root -> env
-    std::vector<int> h_pile_env;          // [n_pile] pile env -> env
-    std::vector<int> h_cenv_env, h_cenv_row;   // coupled env k (env order) -> env, its row of d_env
-    float* d_crep_cenv = nullptr;         // [2 MG_ENV_MAXCT_WIDE][MG_CREP_N][n_coupled], column = row of d_env
-    int* d_crep_cenv_n = nullptr;         // [n_coupled]
-    int* d_crep_col = nullptr;            // [n_coupled] coupled env k -> its column
-    float* d_crep_pile = nullptr;         // [MG_PILE_MAXPT][MG_CREP_N][n_pile]
-    int* d_crep_pile_n = nullptr;         // [n_pile]
-    float* d_crep_free = nullptr;         // [MG_CREP_FREE_CAP][MG_CREP_N][nf_rigid]
-    int* d_crep_free_n = nullptr;         // [nf_rigid]
-    int* d_crep_env = nullptr;            // [owners] owner -> env
-    int* d_crep_blk = nullptr;            // [blocks] pass 1 -> pass 2
-    mg_rigid_contact* d_crep_out = nullptr;
-    int* d_crep_hdr = nullptr;            // [2]
-    int* h_crep_hdr = nullptr;            // [2] mapped, page-locked
+    HostBuf<int> h_crep_hdr;            // [2] mapped, page-locked
     int* d_crep_hdr_alias = nullptr;      // its device address
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -351,10 +385,6 @@ struct mg_sim {
     int kern_n[kRing] = {};
     int kern_miss[kRing] = {};    // launches of that simulate past kKern (untimed)
     long long ring_n = 0;
-    // coupled env k (env order) -> its row of d_env and the float offset /
-    // length of its contact-table record (mg_debug_copy_env_ctab)
-    std::vector<long long> cenv_ctab_off;
-    std::vector<int> cenv_ctab_n;
 };
 
 namespace {
@@ -399,15 +429,13 @@ MgStep make_step(const mg_sim_params& p) {
 
 int ensure_stage(mg_sim* s, size_t nfloat, size_t nidx) {
     if (nfloat > s->stage_n) {
-        if (s->d_stage) (void)hipFree(s->d_stage);
-        s->d_stage = nullptr;
-        HIP_TRY(dalloc(&s->d_stage, nfloat));
+        s->stage_n = 0;
+        HIP_TRY(s->d_stage.alloc(nfloat));
         s->stage_n = nfloat;
     }
     if (nidx > s->stage_idx_n) {
-        if (s->d_stage_idx) (void)hipFree(s->d_stage_idx);
-        s->d_stage_idx = nullptr;
-        HIP_TRY(dalloc(&s->d_stage_idx, nidx));
+        s->stage_idx_n = 0;
+        HIP_TRY(s->d_stage_idx.alloc(nidx));
         s->stage_idx_n = nidx;
     }
     return MG_OK;
@@ -439,10 +467,8 @@ int pin_h2d(mg_sim* s, int n, const void* const* src, const size_t* bytes, void*
     for (int k = 0; k < n; ++k) total += (bytes[k] + 255) & ~(size_t)255;
     if (total > s->h_pin_n) {
         if (s->pin_ev_pending) HIP_TRY(hipEventSynchronize(s->pin_ev));
-        if (s->h_pin) (void)hipHostFree(s->h_pin);
-        s->h_pin = nullptr;
         s->h_pin_n = 0;
-        HIP_TRY(hipHostMalloc((void**)&s->h_pin, total, hipHostMallocDefault));
+        HIP_TRY(s->h_pin.alloc(total, false));
         s->h_pin_n = total;
     }
     if (!s->pin_ev) HIP_TRY(hipEventCreateWithFlags(&s->pin_ev, hipEventDisableTiming));
@@ -493,7 +519,7 @@ int flush_root(mg_sim* s, hipStream_t st) {
     if (!s->pend_root) return MG_OK;
     const float* src = s->pend_root;
     s->pend_root = nullptr;
-    HIP_TRY(mg_launch_scatter_rows(src, MG_STATE_N, s->d_actor_root, nullptr, s->na, s->na, s->d_state, s->nb, st));
+    HIP_TRY(mg_launch_scatter_rows(src, MG_STATE_N, s->d_actor_root, nullptr, s->layout.na, s->layout.na, s->d_state, s->layout.nb, st));
     if (src == s->d_root_in_alias) {   // the mapped input buffer's reader
         HIP_TRY(hipEventRecord(s->root_ev, st));
         s->root_ev_pending = true;
@@ -506,7 +532,7 @@ int flush_tgt(mg_sim* s, int k, hipStream_t st) {
     if (!s->pend_tgt[k]) return MG_OK;
     const float* src = s->pend_tgt[k];
     s->pend_tgt[k] = nullptr;
-    HIP_TRY(hipMemcpyAsync(s->d_dof_tgt + (size_t)k * s->nd, src, (size_t)s->nd * sizeof(float),
+    HIP_TRY(hipMemcpyAsync(s->d_dof_tgt + (size_t)k * s->layout.nd, src, (size_t)s->layout.nd * sizeof(float),
                            hipMemcpyDeviceToDevice, st));
     return MG_OK;
 }
@@ -514,62 +540,20 @@ int flush_tgt(mg_sim* s, int k, hipStream_t st) {
 int set_dof_columns(mg_sim* s, const float* src, int src_host, int ncol, float* dst0, float* dst1,
                     const int* idx, int n_idx, hipStream_t st) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (s->nd == 0) return MG_OK;
+    if (s->layout.nd == 0) return MG_OK;
     if (!src) return fail(MG_ERR_ARG, "null source tensor");
     if (idx && n_idx < 0) return fail(MG_ERR_ARG, "negative index count");
     HIP_TRY(hipSetDevice(s->device));
     const float* dsrc;
     const int* didx;
-    int rc = stage_src(s, src, src_host, (size_t)s->nd * ncol, idx, n_idx, st, &dsrc, &didx);
+    int rc = stage_src(s, src, src_host, (size_t)s->layout.nd * ncol, idx, n_idx, st, &dsrc, &didx);
     if (rc) return rc;
     float* dst[2] = {dst0, dst1};
     if (idx)
-        HIP_TRY(mg_launch_scatter_dofs(dsrc, ncol, s->d_actor_dof, didx, n_idx, s->na, s->max_actor_dofs, dst, st));
+        HIP_TRY(mg_launch_scatter_dofs(dsrc, ncol, s->d_actor_dof, didx, n_idx, s->layout.na, s->layout.max_actor_dofs, dst, st));
     else
-        HIP_TRY(mg_launch_scatter_dofs(dsrc, ncol, nullptr, nullptr, s->nd, 0, 1, dst, st));
+        HIP_TRY(mg_launch_scatter_dofs(dsrc, ncol, nullptr, nullptr, s->layout.nd, 0, 1, dst, st));
     return MG_OK;
-}
-
-// Shape-frame box of a shape (the coupled step's pair screen, mg_env.hip
-// obb_apart; oracle: shape_obb_): centre and half extents; a hull's from the
-// min / max of its vertices
-void shape_obb(const float* sh, const float* hulls, float* o) {
-    const int t = (int)sh[0];
-    for (int k = 0; k < MG_OBB_N; ++k) o[k] = 0.0f;
-    if (t == MG_SHAPE_CONVEX && hulls) {
-        const float* hv = hulls + (int)sh[2];
-        const int nv = (int)hv[0];
-        float lo[3], hi[3];
-        for (int c = 0; c < 3; ++c) { lo[c] = hv[MG_HULL_HEADER + c]; hi[c] = lo[c]; }
-        for (int i = 1; i < nv; ++i)
-            for (int c = 0; c < 3; ++c) {
-                const float v = hv[MG_HULL_HEADER + 3 * i + c];
-                lo[c] = std::min(lo[c], v);
-                hi[c] = std::max(hi[c], v);
-            }
-        for (int c = 0; c < 3; ++c) {
-            o[c] = 0.5f * (lo[c] + hi[c]);
-            o[3 + c] = 0.5f * (hi[c] - lo[c]);
-        }
-    } else if (t == MG_SHAPE_BOX) {
-        o[3] = sh[1]; o[4] = sh[2]; o[5] = sh[3];
-    } else if (t == MG_SHAPE_CAPSULE) {
-        o[3] = sh[1] + sh[2]; o[4] = sh[1]; o[5] = sh[1];
-    } else {
-        o[3] = sh[1]; o[4] = sh[1]; o[5] = sh[1];
-    }
-}
-
-void free_all(mg_sim* s) {
-    void* ptrs[] = {s->d_state, s->d_mass, s->d_body_tmpl, s->d_free_global, s->d_perm, s->d_tbf, s->d_trec, s->d_tbi, s->d_shapes, s->d_hulls, s->d_shape_obb,
-                    s->d_actor_root, s->d_root_row, s->d_slot_global, s->d_slot_actor, s->d_slot_rec, s->d_body_actor, s->d_actor_dof, s->d_cforce, s->d_ext, s->d_dof, s->d_dof_tgt, s->d_dof_frc,
-                    s->d_dof_props, s->d_artic, s->d_artic_step, s->d_env, s->d_pairs, s->d_fpatch, s->d_gpatch, s->d_chain_uni, s->d_fp_mask, s->d_env_carry, s->d_env_ctab, s->d_link_f, s->d_link_i, s->d_stage, s->d_stage_idx, s->d_host_out,
-                    s->d_pile_i, s->d_pile_body, s->d_pile_pairs, s->d_pile_slots, s->d_rstate, s->d_rshapes, s->d_env_shape_first, s->d_cams,
-                    s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out, s->d_ctorque,
-                    s->d_crep_cenv, s->d_crep_cenv_n, s->d_crep_col, s->d_crep_free, s->d_crep_free_n, s->d_crep_pile, s->d_crep_pile_n, s->d_crep_env, s->d_crep_blk, s->d_crep_out, s->d_crep_hdr};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (s->h_crep_hdr) (void)hipHostFree(s->h_crep_hdr);
 }
 
 }  // namespace
@@ -578,6 +562,7 @@ extern "C" {
 
 int32_t mg_abi_version(void) { return MG_ABI_VERSION; }
 const char* mg_last_error(void) { return g_err.c_str(); }
+int32_t mg_last_error_code(void) { return g_err_code; }
 
 int32_t mg_device_count(void) {
     int n = 0;
@@ -611,7 +596,7 @@ void mg_destroy_sim(mg_sim* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    free_all(s);
+    // the buffers go with the sim below (DevBuf, HostBuf)
     for (int k = 0; k < mg_sim::kRing; ++k) {
         if (s->ring_b[k]) (void)hipEventDestroy(s->ring_b[k]);
         if (s->ring_e[k]) (void)hipEventDestroy(s->ring_e[k]);
@@ -623,16 +608,8 @@ void mg_destroy_sim(mg_sim* s) {
     if (s->rev_b) (void)hipEventDestroy(s->rev_b);
     if (s->rev_e) (void)hipEventDestroy(s->rev_e);
     if (s->pin_ev) (void)hipEventDestroy(s->pin_ev);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
     if (s->root_ev) (void)hipEventDestroy(s->root_ev);
-    if (s->h_root_in) (void)hipHostFree(s->h_root_in);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->attr_ev) (void)hipEventDestroy(s->attr_ev);
-    if (s->h_attr) (void)hipHostFree(s->h_attr);
-    if (s->d_attr) (void)hipFree(s->d_attr);
-    if (s->d_attr_idx) (void)hipFree(s->d_attr_idx);
-    if (s->d_artic_split) (void)hipFree(s->d_artic_split);
-    if (s->d_artic_jsplit) (void)hipFree(s->d_artic_jsplit);
     delete s;
 }
 
@@ -643,21 +620,11 @@ int32_t mg_set_sim_params(mg_sim* s, const mg_sim_params* p) {
 }
 
 // k_artic_chain's shared constants (mg_chainlink.h). Link mass constants and
-// the gravity flag: from the stepped instances' global rows, when they all
-// agree (set once: mass properties are fixed after upload).
+// the gravity flag of a group whose stepped instances agree on them
+// (MgArticGroup::uni_mass), from the first one's global rows.
 static void chain_uni_mass(const mg_model* m, ArticGroup& g) {
     const int b0 = g.step_body0[0];
-    bool ok = true;
     const float grav = m->tmpl_body_f[(size_t)m->body_tmpl[b0] * MG_TBODY_F_N + 4];
-    for (size_t i = 1; i < g.step_body0.size() && ok; ++i) {
-        const int bi = g.step_body0[i];
-        ok = m->tmpl_body_f[(size_t)m->body_tmpl[bi] * MG_TBODY_F_N + 4] == grav;
-        for (int l = 1; l < g.nl && ok; ++l)
-            ok = std::memcmp(m->body_mass + (size_t)(bi + l) * MG_MASS_N, m->body_mass + (size_t)(b0 + l) * MG_MASS_N,
-                             MG_MASS_N * sizeof(float)) == 0;
-    }
-    g.uni_mass = ok;
-    if (!ok) return;
     for (int l = 1; l < g.nl; ++l) {
         const float* r = m->body_mass + (size_t)(b0 + l) * MG_MASS_N;
         const ChainLink k = chain_link_make(r[11], v3(r[8], r[9], r[10]), r[1], r[2], r[3], q4(r[4], r[5], r[6], r[7]));
@@ -683,7 +650,7 @@ static void chain_uni_dof(const float* props, ArticGroup& g) {
     for (int d = 0; d < g.ndof; ++d)
         for (int j = 0; j < 9; ++j) g.uni[MG_CHAIN_UNI_DOF + 9 * d + j] = props[(size_t)(d0 + d) * MG_DOFPROP_N + j];
 }
-static hipError_t chain_uni_upload(mg_sim* s) {
+static hipError_t chain_uni_upload(Model* s) {
     if (!s->d_chain_uni) return hipSuccess;
     std::vector<float> u(s->groups.size() * MG_CHAIN_UNI_N, 0.0f);
     for (size_t i = 0; i < s->groups.size(); ++i)
@@ -706,8 +673,8 @@ struct JfrPlan {
     std::vector<std::array<int, 2>> ec;        // per EnvGroup: flag, actor
     bool changed = false;
 };
-static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
-    const int nd = s->nd;
+static int jfr_plan(const Model* s, const float* props, JfrPlan& pl) {
+    const int nd = s->layout.nd;
     for (int d = 0; d < nd; ++d) {
         const float f = props[(size_t)d * MG_DOFPROP_N + 9];
         if (!(std::isfinite(f) && f >= 0.0f))
@@ -720,8 +687,8 @@ static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
         return -1;
     };
     auto actor_of = [&](int d) {
-        const auto it = std::upper_bound(s->h_actor_dof.begin(), s->h_actor_dof.end(), d);
-        return (int)(it - s->h_actor_dof.begin()) - 1;
+        const auto it = std::upper_bound(s->layout.actor_dof.begin(), s->layout.actor_dof.end(), d);
+        return (int)(it - s->layout.actor_dof.begin()) - 1;
     };
     pl.gc.assign(s->groups.size(), {0, 0, -1});
     std::vector<std::vector<char>> owns(s->groups.size());
@@ -729,7 +696,7 @@ static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
         const ArticGroup& g = s->groups[gi];
         owns[gi].assign((size_t)g.step_count, 0);
         for (int k = 0; pl.ndof > 0 && k < g.step_count; ++k) {
-            const int d = fric_dof(s->h_artic_step[(size_t)(g.step_offset + k) * MG_ARTIC_I_N + 1], g.ndof);
+            const int d = fric_dof(s->layout.artic_step[(size_t)(g.step_offset + k) * MG_ARTIC_I_N + 1], g.ndof);
             if (d < 0) continue;
             owns[gi][k] = 1;
             pl.lanes++;
@@ -737,14 +704,14 @@ static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
         }
     }
     if (pl.lanes > 0) {
-        pl.split.resize(s->h_artic_step.size());
+        pl.split.resize(s->layout.artic_step.size());
         for (size_t gi = 0; gi < s->groups.size(); ++gi) {
             const ArticGroup& g = s->groups[gi];
             int* dst = pl.split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
             for (int pass = 0; pass < 2; ++pass)
                 for (int k = 0; k < g.step_count; ++k) {
                     if ((owns[gi][k] != 0) != (pass == 1)) continue;
-                    std::memcpy(dst, s->h_artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
+                    std::memcpy(dst, s->layout.artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
                                 MG_ARTIC_I_N * sizeof(int));
                     dst += MG_ARTIC_I_N;
                     pl.gc[gi][pass]++;
@@ -756,7 +723,7 @@ static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
         const EnvGroup& g = s->env_groups[gi];
         if (g.tmpl < 0 || pl.ndof == 0) continue;
         for (int r = g.offset; r < g.offset + g.count && !pl.ec[gi][0]; ++r) {
-            const int d = fric_dof(s->h_env_d0[r], g.ndof);
+            const int d = fric_dof(s->layout.env_d0[r], g.ndof);
             if (d >= 0) pl.ec[gi] = {1, actor_of(d)};
         }
         if (pl.ec[gi][0]) pl.envs += g.count;
@@ -765,23 +732,15 @@ static int jfr_plan(const mg_sim* s, const float* props, JfrPlan& pl) {
     for (size_t gi = 0; gi < s->env_groups.size(); ++gi) pl.changed = pl.changed || pl.ec[gi][0] != s->env_groups[gi].jfr;
     return MG_OK;
 }
-static int jfr_commit(mg_sim* s, JfrPlan& pl) {
+static int jfr_commit(Model* s, JfrPlan& pl) {
     if (pl.changed) {
-        int* fresh = nullptr;
-        if (!pl.split.empty()) {
-            HIP_TRY(dalloc(&fresh, pl.split.size()));
-            if (hipMemcpy(fresh, pl.split.data(), pl.split.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(fresh);
-                return fail(MG_ERR_DEVICE, "joint friction routing: copy failed");
-            }
-        }
+        DevBuf<int> fresh;
+        if (!pl.split.empty() && fresh.upload(pl.split) != hipSuccess)
+            return fail(MG_ERR_DEVICE, "joint friction routing: copy failed");
         // no step may still read the rows this replaces
-        if (hipDeviceSynchronize() != hipSuccess) {
-            if (fresh) (void)hipFree(fresh);
+        if (hipDeviceSynchronize() != hipSuccess)
             return fail(MG_ERR_DEVICE, "joint friction routing: device synchronize failed");
-        }
-        if (s->d_artic_jsplit) (void)hipFree(s->d_artic_jsplit);
-        s->d_artic_jsplit = fresh;
+        s->d_artic_jsplit = std::move(fresh);
         s->h_jsplit.swap(pl.split);
     }
     for (size_t gi = 0; gi < s->groups.size(); ++gi) {
@@ -813,8 +772,8 @@ static int jfr_refusal(const mg_sim* s) {
         else if (s->n_sens > 0 && s->sens_tmpl_env[g.tmpl]) what = "a force sensor";
         else if (s->n_attr_env > 0)
             for (const mg_attractor& a : s->attrs) {
-                const int ar = s->h_body_class[a.body] == ATTR_ENV_LINK ? s->h_body_artic[a.body] : -1;
-                if (ar >= 0 && s->h_artic_info[ar].tmpl == g.tmpl) what = "an attractor";
+                const int ar = s->layout.body_class[a.body] == ATTR_ENV_LINK ? s->layout.body_artic[a.body] : -1;
+                if (ar >= 0 && s->layout.artic_info[ar].tmpl == g.tmpl) what = "an attractor";
             }
         if (what)
             return fail(MG_ERR_UNSUPPORTED, "actor %d: joint friction (DOF friction > 0) together with %s on the same "
@@ -823,771 +782,90 @@ static int jfr_refusal(const mg_sim* s) {
     return MG_OK;
 }
 
+// Plan, then commit: mg_plan_layout derives every table on
+// the host; the device buffers are filled into a Model built apart, which
+// becomes the sim's only when every HIP call has succeeded. A refused or
+// failed upload leaves the sim as it was (and frees what it had allocated).
 int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     if (!s || !m) return fail(MG_ERR_ARG, "null argument");
     if (s->uploaded) return fail(MG_ERR_STATE, "model already uploaded");
-    s->h_pile_env.clear();
-    s->h_cenv_env.clear();
-    if (m->num_bodies < 0 || m->num_actors < 0 || m->num_dofs < 0) return fail(MG_ERR_ARG, "negative sizes");
+    Model M;
+    MgLayout& L = M.layout;
+    std::string err;
+    if (int rc_ = mg_plan_layout(s->params, *m, layout_sizes(), L, err)) return fail(rc_, "%s", err.c_str());
     HIP_TRY(hipSetDevice(s->device));
-    const int nb = m->num_bodies, na = m->num_actors, nd = m->num_dofs;
-    s->nenv = m->num_envs; s->na = na; s->nb = nb; s->nd = nd;
-    s->ntb = m->num_tmpl_bodies; s->ns = m->num_shapes;
-    s->nartic = m->num_artics; s->ntl = m->num_tmpl_links;
+    const int nb = L.nb, na = L.na, nd = L.nd;
+    for (MgArticGroup& g : L.groups) M.groups.emplace_back(std::move(g));
+    for (const MgEnvGroup& g : L.env_groups) M.env_groups.emplace_back(g);
+    L.groups.clear();
+    L.env_groups.clear();
+    for (ArticGroup& g : M.groups)
+        if (g.uni_mass) {
+            chain_uni_mass(m, g);
+            chain_uni_dof(m->dof_props, g);
+        }
 
-    // validate indices on the host before anything reaches a kernel
-    for (int b = 0; b < nb; ++b) {
-        const int t = m->body_tmpl[b];
-        if (t < 0 || t >= s->ntb) return fail(MG_ERR_ARG, "body %d: template %d out of range", b, t);
-        const int s0 = m->tmpl_body_i[t * MG_TBODY_I_N + 0], sc = m->tmpl_body_i[t * MG_TBODY_I_N + 1];
-        if (s0 < 0 || sc < 0 || s0 + sc > s->ns) return fail(MG_ERR_ARG, "template body %d: bad shape range", t);
-    }
-    for (int k = 0; k < s->ns; ++k) {
-        const float* sh = m->shapes + (size_t)k * MG_SHAPE_STRIDE;
-        const int t = (int)sh[0];
-        if (t < MG_SHAPE_SPHERE || t > MG_SHAPE_CONVEX) return fail(MG_ERR_ARG, "shape %d: unknown type %d", k, t);
-        if (t != MG_SHAPE_CONVEX) continue;
-        const long off = (long)sh[2], nh = m->hulls ? m->num_hull_floats : 0;
-        if (off < 0 || off + MG_HULL_HEADER > nh) return fail(MG_ERR_ARG, "shape %d: hull offset %ld out of range", k, off);
-        const int nv = (int)m->hulls[off], nfc = (int)m->hulls[off + 1], ned = (int)m->hulls[off + 2];
-        if (nv < 4 || nv > MG_HULL_MAX_VERTS || nfc < 4 || nfc > MG_HULL_MAX_FACES || ned < 0 ||
-            ned > 3 * MG_HULL_MAX_VERTS || off + MG_HULL_HEADER + 3L * nv + 4L * nfc + 2L * ned > nh)
-            return fail(MG_ERR_ARG, "shape %d: bad hull record (%d vertices, %d faces, %d edges)", k, nv, nfc, ned);
-        for (int e = 0; e < 2 * ned; ++e) {
-            const float vi = m->hulls[off + MG_HULL_HEADER + 3L * nv + 4L * nfc + e];
-            if (!(vi >= 0.0f && vi < (float)nv)) return fail(MG_ERR_ARG, "shape %d: hull edge vertex out of range", k);
-        }
-    }
-    for (int a = 0; a < na; ++a) {
-        if (m->actor_root_body[a] < 0 || m->actor_root_body[a] >= nb) return fail(MG_ERR_ARG, "actor %d: bad root", a);
-        if (m->actor_dof[a] > m->actor_dof[a + 1]) return fail(MG_ERR_ARG, "actor_dof not monotone");
-        s->max_actor_dofs = std::max(s->max_actor_dofs, m->actor_dof[a + 1] - m->actor_dof[a]);
-    }
-    if (na > 0 && (m->actor_dof[0] != 0 || m->actor_dof[na] != nd)) return fail(MG_ERR_ARG, "actor_dof must span [0, num_dofs]");
-
-    // ---- coupled envs: envs where two bodies may touch (actor_coll rule, see
-    // migym.h) step in the per-env kernel; everything else in the free-body /
-    // articulation kernels
-    std::vector<char> coupled_body(nb, 0);           // free roots / articulation roots of coupled envs
-    std::vector<std::array<int, MG_ENV_I_N>> env_rows;   // global body ids, converted below
-    std::vector<int> env_tmpl;
-    std::vector<int> pairs;                              // [..][4] shape pairs of the coupled envs
-    // pile envs (mg_pile.hip): rows with global body ids (converted below),
-    // the free bodies, their candidate pairs
-    std::vector<std::array<int, MG_PILE_I_N>> pile_rows;
-    std::vector<int> pile_body, pile_slots;
-    std::vector<unsigned> pile_pairs;
-    // envs built alike (the same shapes, filters and order) share one slot table
-    // and pair list: 4096 pyramids read one 2 KB list through L2
-    std::map<std::pair<std::vector<int>, std::vector<unsigned>>, std::pair<int, int>> pile_list_at;
-    if (m->actor_coll && na > 0) {
-        for (int a = 0; a + 1 < na; ++a)
-            if (m->actor_root_body[a + 1] <= m->actor_root_body[a])
-                return fail(MG_ERR_ARG, "actor_coll needs actors in body order");
-        std::vector<int> artic_of_root(nb, -1);
-        for (int k = 0; k < m->num_artics; ++k) {
-            const int r0 = m->artic_i[(size_t)k * MG_ARTIC_I_N + 0];
-            if (r0 < 0 || r0 >= nb) return fail(MG_ERR_ARG, "articulation %d: bad first body", k);
-            artic_of_root[r0] = k;
-        }
-        const int ne = m->num_envs;
-        std::vector<std::vector<int>> env_actors(ne > 0 ? ne : 0);
-        for (int a = 0; a < na; ++a) {
-            const int e = m->actor_coll[(size_t)a * MG_ACOLL_N + 0];
-            if (e < 0 || e >= ne) return fail(MG_ERR_ARG, "actor %d: env %d out of range", a, e);
-            env_actors[e].push_back(a);
-        }
-        auto collide = [m](int a, int b) {
-            const int ga = m->actor_coll[(size_t)a * MG_ACOLL_N + 1], gb = m->actor_coll[(size_t)b * MG_ACOLL_N + 1];
-            const int fa = m->actor_coll[(size_t)a * MG_ACOLL_N + 2], fb = m->actor_coll[(size_t)b * MG_ACOLL_N + 2];
-            return (ga == gb || ga == -1 || gb == -1) && (fa & fb) == 0;
-        };
-        for (int e = 0; e < ne; ++e) {
-            std::vector<int> art, fr, stc;
-            for (int a : env_actors[e]) {
-                const int r0 = m->actor_root_body[a];
-                const int kind = m->body_kind[r0];
-                if (kind == MG_BODY_LINK) art.push_back(a);
-                else if (kind == MG_BODY_FREE) fr.push_back(a);
-                else stc.push_back(a);
-            }
-            bool coupled = false;
-            for (size_t i = 0; i < fr.size(); ++i) {
-                for (int t : stc) coupled = coupled || collide(fr[i], t);
-                for (size_t j = i + 1; j < fr.size(); ++j) coupled = coupled || collide(fr[i], fr[j]);
-            }
-            for (int a : art) {
-                for (int t : stc) coupled = coupled || collide(a, t);
-                for (int f : fr) coupled = coupled || collide(a, f);
-                // a floating-base articulation always steps here (ground contacts,
-                // the root's own dynamics)
-                const int k = artic_of_root[m->actor_root_body[a]];
-                if (k >= 0 && !m->artic_tmpl_i[m->artic_i[(size_t)k * MG_ARTIC_I_N + 2] * MG_ATMPL_I_N + 3])
-                    coupled = true;
-            }
-            if (!coupled) continue;
-            if (art.empty() && fr.size() > MG_ENV_MAXF) {
-                // a pile (mg_pile.hip): lane k = free body k; pairs
-                // per free body k and shape of k: the ground, the static bodies it
-                // may touch, the later free bodies it may touch
-                if (fr.size() > MG_PILE_MAXB || stc.size() > MG_ENV_MAXS)
-                    return fail(MG_ERR_UNSUPPORTED,
-                                "env %d: %zu free / %zu static bodies in contact range; a pile env supports %d / %d",
-                                e, fr.size(), stc.size(), MG_PILE_MAXB, MG_ENV_MAXS);
-                std::array<int, MG_PILE_I_N> row;
-                row.fill(0);
-                row[0] = (int)pile_body.size();
-                row[1] = (int)fr.size();
-                row[4] = (int)stc.size();
-                for (size_t t = 0; t < stc.size(); ++t) row[5 + t] = m->actor_root_body[stc[t]];
-                for (int f : fr) {
-                    pile_body.push_back(m->actor_root_body[f]);
-                    coupled_body[m->actor_root_body[f]] = 1;
-                }
-                const bool ground = s->params.has_ground != 0;
-                auto shp = [m](int b, int* s0, int* ns) {
-                    const int* t = m->tmpl_body_i + (size_t)m->body_tmpl[b] * MG_TBODY_I_N;
-                    *s0 = t[0];
-                    *ns = t[1];
-                };
-                // local shape slots: the free bodies' shapes in body order, then the statics'
-                std::vector<int> slots;
-                std::vector<int> first_slot(fr.size() + stc.size());
-                for (size_t k = 0; k < fr.size() + stc.size(); ++k) {
-                    const bool st = k >= fr.size();
-                    int sb0, nsb;
-                    shp(m->actor_root_body[st ? stc[k - fr.size()] : fr[k]], &sb0, &nsb);
-                    first_slot[k] = (int)slots.size() / 2;
-                    for (int sb = sb0; sb < sb0 + nsb; ++sb) {
-                        slots.push_back(st ? MG_PILE_ST0 + (int)(k - fr.size()) : (int)k);
-                        slots.push_back(sb);
-                    }
-                }
-                if ((int)slots.size() / 2 > MG_PILE_MAXSH)
-                    return fail(MG_ERR_UNSUPPORTED, "env %d: %zu collision shapes; a pile env supports %d", e,
-                                slots.size() / 2, MG_PILE_MAXSH);
-                std::vector<unsigned> plist;
-                for (int k = 0; k < (int)fr.size(); ++k) {
-                    int sa0, nsa;
-                    shp(m->actor_root_body[fr[k]], &sa0, &nsa);
-                    for (int sa = sa0; sa < sa0 + nsa; ++sa) {
-                        const unsigned la = (unsigned)(first_slot[k] + (sa - sa0));
-                        auto push = [&](int owner, int sb, int sb0) {
-                            plist.push_back(la | (unsigned)(first_slot[owner] + (sb - sb0)) << 8);
-                        };
-                        if (ground) plist.push_back(la | (unsigned)MG_PILE_GROUND << 8);
-                        for (int t = 0; t < (int)stc.size(); ++t) {
-                            if (!collide(fr[k], stc[t])) continue;
-                            int sb0, nsb;
-                            shp(m->actor_root_body[stc[t]], &sb0, &nsb);
-                            for (int sb = sb0; sb < sb0 + nsb; ++sb) push((int)fr.size() + t, sb, sb0);
-                        }
-                        for (int j = k + 1; j < (int)fr.size(); ++j) {
-                            if (!collide(fr[k], fr[j])) continue;
-                            int sb0, nsb;
-                            shp(m->actor_root_body[fr[j]], &sb0, &nsb);
-                            for (int sb = sb0; sb < sb0 + nsb; ++sb) push(j, sb, sb0);
-                        }
-                    }
-                }
-                row[3] = (int)plist.size();
-                row[10] = (int)slots.size() / 2;
-                if (row[3] > MG_PILE_MAXPAIRS)
-                    return fail(MG_ERR_UNSUPPORTED, "env %d: %d candidate shape pairs; a pile env supports %d", e,
-                                row[3], MG_PILE_MAXPAIRS);
-                auto key = std::make_pair(slots, plist);
-                auto it = pile_list_at.find(key);
-                if (it != pile_list_at.end()) {
-                    row[2] = it->second.first;
-                    row[9] = it->second.second;
-                } else {
-                    row[2] = (int)pile_pairs.size();
-                    row[9] = (int)pile_slots.size() / 2;
-                    pile_list_at.emplace(std::move(key), std::make_pair(row[2], row[9]));
-                    pile_pairs.insert(pile_pairs.end(), plist.begin(), plist.end());
-                    pile_slots.insert(pile_slots.end(), slots.begin(), slots.end());
-                }
-                pile_rows.push_back(row);
-                s->h_pile_env.push_back(e);
-                continue;
-            }
-            if (art.size() > 1 || fr.size() > MG_ENV_MAXF || stc.size() > MG_ENV_MAXS)
-                return fail(MG_ERR_UNSUPPORTED,
-                            "env %d: %zu articulations / %zu free / %zu static bodies in contact range; the "
-                            "coupled step supports 1 / %d / %d", e, art.size(), fr.size(), stc.size(),
-                            MG_ENV_MAXF, MG_ENV_MAXS);
-            int art_nl = 0, art_nd = 0, art_fb = 0, art_fl = 0;
-            if (!art.empty()) {
-                const int k = artic_of_root[m->actor_root_body[art[0]]];
-                const int t = k >= 0 ? m->artic_i[(size_t)k * MG_ARTIC_I_N + 2] : -1;
-                if (t < 0 || t >= m->num_artic_tmpls) return fail(MG_ERR_ARG, "env %d: bad articulation", e);
-                art_nl = m->artic_tmpl_i[t * MG_ATMPL_I_N + 1];
-                art_nd = m->artic_tmpl_i[t * MG_ATMPL_I_N + 2];
-                art_fb = m->artic_tmpl_i[t * MG_ATMPL_I_N + 3] ? 0 : 1;
-                const int fl = m->artic_tmpl_i[t * MG_ATMPL_I_N + 0];
-                if (fl < 0 || art_nl < 1 || fl + art_nl > m->num_tmpl_links)
-                    return fail(MG_ERR_ARG, "env %d: bad articulation template %d", e, t);
-                art_fl = fl;
-            }
-            if (art_nd + 6 * art_fb + 6 * (int)fr.size() > MG_ENV_SLOTS_WIDE || art_nl > MG_MAX_LINKS)
-                return fail(MG_ERR_UNSUPPORTED, "env %d: %d links, %d DOFs%s + %zu free bodies exceed the %d links / %d "
-                            "velocity slots of the coupled step", e, art_nl, art_nd, art_fb ? " + a floating base" : "",
-                            fr.size(), MG_MAX_LINKS, MG_ENV_SLOTS_WIDE);
-            std::array<int, MG_ENV_I_N> row;
-            row.fill(0);
-            row[0] = -1;
-            int tmpl = -1;
-            if (!art.empty()) {
-                const int r0 = m->actor_root_body[art[0]];
-                const int k = artic_of_root[r0];
-                if (k < 0) return fail(MG_ERR_ARG, "env %d: articulated actor without articulation record", e);
-                row[0] = r0;
-                row[1] = m->artic_i[(size_t)k * MG_ARTIC_I_N + 1];
-                tmpl = m->artic_i[(size_t)k * MG_ARTIC_I_N + 2];
-                coupled_body[r0] = 1;
-            }
-            row[2] = (int)fr.size();
-            for (size_t i = 0; i < fr.size(); ++i) {
-                row[3 + i] = m->actor_root_body[fr[i]];
-                coupled_body[row[3 + i]] = 1;
-            }
-            row[7] = (int)stc.size();
-            for (size_t i = 0; i < stc.size(); ++i) row[8 + i] = m->actor_root_body[stc[i]];
-            int mask = 0;
-            static const int pair_bit[4][4] = {{-1, 0, 1, 2}, {-1, -1, 3, 4}, {-1, -1, -1, 5}, {-1, -1, -1, -1}};
-            for (size_t i = 0; i < fr.size(); ++i) {
-                if (!art.empty() && collide(art[0], fr[i])) mask |= 1 << i;
-                for (size_t j = i + 1; j < fr.size(); ++j)
-                    if (collide(fr[i], fr[j])) mask |= 1 << (8 + pair_bit[i][j]);
-                for (size_t t = 0; t < stc.size(); ++t)
-                    if (collide(fr[i], stc[t])) mask |= 1 << (14 + 4 * i + t);
-            }
-            for (size_t t = 0; t < stc.size(); ++t)
-                if (!art.empty() && collide(art[0], stc[t])) mask |= 1 << (4 + t);
-            row[12] = mask;
-            row[13] = tmpl;
-            // candidate shape pairs, in the order the step solves them
-            auto shp = [m](int b, int* s0, int* ns) {
-                const int* t = m->tmpl_body_i + (size_t)m->body_tmpl[b] * MG_TBODY_I_N;
-                *s0 = t[0];
-                *ns = t[1];
-            };
-            auto push = [&pairs](int a, int sa, int b, int sb) {
-                pairs.push_back(a); pairs.push_back(sa); pairs.push_back(b); pairs.push_back(sb);
-            };
-            static const int pbit[4][4] = {{-1, 0, 1, 2}, {-1, -1, 3, 4}, {-1, -1, -1, 5}, {-1, -1, -1, -1}};
-            const bool ground = s->params.has_ground != 0;
-            row[14] = (int)(pairs.size() / 4);
-            for (int k = 0; k < (int)fr.size(); ++k) {
-                int sa0, nsa;
-                shp(row[3 + k], &sa0, &nsa);
-                for (int sa = sa0; sa < sa0 + nsa; ++sa) {
-                    if (ground) push(MG_ENV_FREE0 + k, sa, -1, -1);
-                    for (int t = 0; t < (int)stc.size(); ++t) {
-                        if (!((mask >> (14 + 4 * k + t)) & 1)) continue;
-                        int sb0, nsb;
-                        shp(row[8 + t], &sb0, &nsb);
-                        for (int sb = sb0; sb < sb0 + nsb; ++sb) push(MG_ENV_FREE0 + k, sa, MG_ENV_STATIC0 + t, sb);
-                    }
-                    for (int j = k + 1; j < (int)fr.size(); ++j) {
-                        if (!((mask >> (8 + pbit[k][j])) & 1)) continue;
-                        int sb0, nsb;
-                        shp(row[3 + j], &sb0, &nsb);
-                        for (int sb = sb0; sb < sb0 + nsb; ++sb) push(MG_ENV_FREE0 + k, sa, MG_ENV_FREE0 + j, sb);
-                    }
-                    if (row[0] >= 0 && !art_fb && ((mask >> k) & 1)) {   // the fixed base (static)
-                        int sb0, nsb;
-                        shp(row[0], &sb0, &nsb);
-                        for (int sb = sb0; sb < sb0 + nsb; ++sb) push(MG_ENV_FREE0 + k, sa, 0, sb);
-                    }
-                }
-            }
-            for (int l = art_fb ? 0 : 1; l < art_nl; ++l) {     // moving links (a floating base moves)
-                // the link's body (virtual links of ball / multi-axis joints: none)
-                const int bl = m->tmpl_link_i[(size_t)(art_fl + l) * MG_LINK_I_N + 3];
-                if (bl < 0) continue;
-                int sa0, nsa;
-                shp(row[0] + bl, &sa0, &nsa);
-                for (int sa = sa0; sa < sa0 + nsa; ++sa) {
-                    if (ground) push(l, sa, -1, -1);
-                    for (int t = 0; t < (int)stc.size(); ++t) {
-                        if (!((mask >> (4 + t)) & 1)) continue;
-                        int sb0, nsb;
-                        shp(row[8 + t], &sb0, &nsb);
-                        for (int sb = sb0; sb < sb0 + nsb; ++sb) push(l, sa, MG_ENV_STATIC0 + t, sb);
-                    }
-                    for (int k = 0; k < (int)fr.size(); ++k) {
-                        if (!((mask >> k) & 1)) continue;
-                        int sb0, nsb;
-                        shp(row[3 + k], &sb0, &nsb);
-                        for (int sb = sb0; sb < sb0 + nsb; ++sb) push(l, sa, MG_ENV_FREE0 + k, sb);
-                    }
-                }
-            }
-            row[15] = (int)(pairs.size() / 4) - row[14];
-            env_rows.push_back(row);
-            s->h_cenv_env.push_back(e);
-            env_tmpl.push_back(tmpl);
-        }
-    }
-
-    // free bodies ordered by template body (stable): bodies of one kind share
-    // waves, so e.g. the servo scene's airborne UAVs and grounded vehicles do
-    // not interleave lane by lane (results do not depend on the order).
-    // Templates whose instances start farthest from the ground plane come
-    // first: a launch larger than one resident round dispatches the array back
-    // to front (mg_launch_rigid_step), i.e. the likely-in-contact (long) waves
-    // first and the airborne (short) ones last, filling the last round's tail.
-    // Free bodies of coupled envs come last (the per-env kernel reads them).
-    std::vector<int> free_ids, free_cpl;
-    for (int b = 0; b < nb; ++b)
-        if (m->body_kind[b] == MG_BODY_FREE) (coupled_body[b] ? free_cpl : free_ids).push_back(b);
-    auto nshapes = [m](int b) { return m->tmpl_body_i[m->body_tmpl[b] * MG_TBODY_I_N + 1]; };
-    std::vector<double> clear_sum(m->num_tmpl_bodies, 0.0);
-    std::vector<int> clear_n(m->num_tmpl_bodies, 0);
-    {
-        const mg_sim_params& p = s->params;
-        float gn[3] = {0.0f, 0.0f, 0.0f};
-        float gd = 0.0f;
-        if (p.has_ground) {
-            for (int k = 0; k < 3; ++k) gn[k] = p.ground_normal[k];
-            gd = p.ground_distance;
-        } else {
-            gn[p.up_axis == 0 ? 1 : 2] = 1.0f;
-        }
-        for (int b : free_ids) {
-            const float* x = m->body_state0 + (size_t)b * MG_STATE_N;
-            clear_sum[m->body_tmpl[b]] += (double)gn[0] * x[0] + (double)gn[1] * x[1] + (double)gn[2] * x[2] + gd;
-            clear_n[m->body_tmpl[b]] += 1;
-        }
-    }
-    auto clearance = [&](int t) { return clear_n[t] ? clear_sum[t] / clear_n[t] : 0.0; };
-    std::stable_sort(free_ids.begin(), free_ids.end(), [&](int a, int b) {
-        const bool ma = nshapes(a) > 1, mb = nshapes(b) > 1;   // single-shape bodies first
-        if (ma != mb) return !ma;
-        const int ta = m->body_tmpl[a], tb = m->body_tmpl[b];
-        if (ta == tb) return false;
-        const double ca = clearance(ta), cb = clearance(tb);
-        if (ca != cb) return ca > cb;
-        return ta < tb;
-    });
-    s->nf1 = 0;
-    for (int b : free_ids) s->nf1 += nshapes(b) <= 1 ? 1 : 0;
-    s->nf_rigid = (int)free_ids.size();
-    free_ids.insert(free_ids.end(), free_cpl.begin(), free_cpl.end());
-    s->nf = (int)free_ids.size();
-
-    // internal storage order: free bodies (as above), articulation links
-    // (instance by instance, template by template), everything else
-    std::vector<int> order(free_ids), perm(nb, -1);
-    std::vector<char> placed(nb, 0);
-    for (int b : free_ids) placed[b] = 1;
-
-    // articulation instances grouped by template
-    s->groups.clear();
-    s->h_body_class.assign(nb, ATTR_NONE);
-    s->h_body_grp.assign(nb, -1);
-    s->h_body_inst.assign(nb, -1);
-    s->h_body_artic.assign(nb, -1);
-    s->h_artic_info.clear();
-    s->h_link_i.assign(m->tmpl_link_i, m->tmpl_link_i + (size_t)s->ntl * MG_LINK_I_N);
-    s->h_atmpl.assign(m->artic_tmpl_i, m->artic_tmpl_i + (size_t)m->num_artic_tmpls * MG_ATMPL_I_N);
-    std::vector<int> artic_sorted, artic_step;
-    for (int t = 0; t < m->num_artic_tmpls; ++t) {
-        ArticGroup g;
-        g.tmpl = t;
-        g.first_link = m->artic_tmpl_i[t * MG_ATMPL_I_N + 0];
-        g.nl = m->artic_tmpl_i[t * MG_ATMPL_I_N + 1];
-        g.ndof = m->artic_tmpl_i[t * MG_ATMPL_I_N + 2];
-        g.fixed_base = m->artic_tmpl_i[t * MG_ATMPL_I_N + 3];
-        if (g.nl < 1 || g.nl > MG_MAX_LINKS || g.ndof > g.nl || g.ndof > MG_MAX_DOFS || g.first_link < 0 ||
-            g.first_link + g.nl > s->ntl)
-            return fail(MG_ERR_UNSUPPORTED, "articulation template %d: %d links / %d dofs unsupported", t, g.nl, g.ndof);
-        g.nbody = 0;
-        for (int l = 0; l < g.nl; ++l) {
-            const int* li = m->tmpl_link_i + (size_t)(g.first_link + l) * MG_LINK_I_N;
-            if (li[0] >= l || (l > 0 && li[0] < 0) || (l == 0 && li[0] != -1))
-                return fail(MG_ERR_ARG, "articulation template %d: links not in topological order", t);
-            if (li[2] >= g.ndof) return fail(MG_ERR_ARG, "articulation template %d: bad dof index", t);
-            // real links carry bodies 0, 1, 2, ... in link order; virtual links
-            // (the first two of a ball joint) are revolute with a DOF and no body
-            if (li[3] >= 0) {
-                if (li[3] != g.nbody) return fail(MG_ERR_ARG, "articulation template %d: link bodies out of order", t);
-                g.nbody++;
-            } else if (l == 0 || li[1] != MG_JOINT_REVOLUTE || li[2] < 0) {
-                return fail(MG_ERR_ARG, "articulation template %d: bad virtual link %d", t, l);
-            }
-        }
-        g.chain = g.fixed_base && g.ndof == g.nl - 1 && g.nbody == g.nl;
-        for (int l = 1; l < g.nl && g.chain; ++l) {
-            const int* li = m->tmpl_link_i + (size_t)(g.first_link + l) * MG_LINK_I_N;
-            g.chain = li[0] == l - 1 && li[2] == l - 1 && (li[1] == MG_JOINT_REVOLUTE || li[1] == MG_JOINT_PRISMATIC);
-        }
-        g.offset = (int)artic_sorted.size() / MG_ARTIC_I_N;
-        g.count = 0;
-        g.step_offset = (int)artic_step.size() / MG_ARTIC_I_N;
-        g.step_count = 0;
-        // Link stride (row field 3): link l of an instance is body first + l * stride.
-        // Instances that step in k_artic_chain (one lane per articulation) are laid
-        // out link-major in blocks of 64, the kernel's wavefront: link l of the
-        // block's instances are 64 consecutive slots, so every per-link load and
-        // store of a wave is one contiguous 256-B access (link-contiguous storage
-        // strides the lanes nl * 4 B apart). Everything else: stride 1.
-        const bool blocked = g.chain && g.nl >= 2 && g.nl <= 4;
-        std::vector<int> blk_k, blk_sorted, blk_step;
-        for (int k = 0; k < m->num_artics; ++k) {
-            const int* ai = m->artic_i + (size_t)k * MG_ARTIC_I_N;
-            if (ai[2] != t) continue;
-            if (ai[0] < 0 || ai[0] + g.nbody > nb || ai[1] < 0 || ai[1] + g.ndof > nd)
-                return fail(MG_ERR_ARG, "articulation %d out of range", k);
-            const bool cpl = coupled_body[ai[0]] != 0;
-            const bool blk = blocked && !cpl;
-            for (int l = 0; l < g.nbody; ++l) s->h_body_artic[ai[0] + l] = (int)s->h_artic_info.size();
-            s->h_artic_info.push_back({ai[0], ai[1], t, cpl ? 1 : 0});
-            if (blk) {
-                blk_k.push_back(k);
-                blk_sorted.push_back((int)artic_sorted.size());
-                blk_step.push_back((int)artic_step.size());
-            }
-            for (int j = 0; j < MG_ARTIC_I_N; ++j) artic_sorted.push_back(j == 3 ? 1 : ai[j]);
-            if (!cpl) {
-                for (int j = 0; j < MG_ARTIC_I_N; ++j) artic_step.push_back(j == 3 ? 1 : ai[j]);
-                g.step_count++;
-                g.step_body0.push_back(ai[0]);
-                g.step_dof0.push_back(ai[1]);
-            }
-            for (int l = 0; l < g.nbody; ++l) {
-                if (placed[ai[0] + l]) return fail(MG_ERR_ARG, "articulation %d overlaps another body", k);
-                placed[ai[0] + l] = 1;
-                if (!blk) order.push_back(ai[0] + l);
-                s->h_body_class[ai[0] + l] = cpl ? ATTR_ENV_LINK : ATTR_LINK;
-                if (!cpl) {
-                    s->h_body_grp[ai[0] + l] = (int)s->groups.size();
-                    s->h_body_inst[ai[0] + l] = g.step_count - 1;
-                }
-            }
-            g.count++;
-        }
-        for (size_t i0 = 0; i0 < blk_k.size(); i0 += 64) {
-            const int cnt = (int)std::min<size_t>(64, blk_k.size() - i0);
-            for (int l = 0; l < g.nbody; ++l)
-                for (int j = 0; j < cnt; ++j) order.push_back(m->artic_i[(size_t)blk_k[i0 + j] * MG_ARTIC_I_N] + l);
-            for (int j = 0; j < cnt; ++j) {
-                artic_sorted[blk_sorted[i0 + j] + 3] = cnt;
-                artic_step[blk_step[i0 + j] + 3] = cnt;
-            }
-        }
-        if (!g.fixed_base && g.step_count > 0)
-            return fail(MG_ERR_UNSUPPORTED, "articulation template %d: a floating base steps in the coupled "
-                        "per-env kernel, which needs actor_coll", t);
-        if (blocked && g.step_count > 0) chain_uni_mass(m, g);
-        s->groups.push_back(g);
-    }
-
-    for (int b = 0; b < nb; ++b)
-        if (!placed[b]) order.push_back(b);
-    for (int i = 0; i < nb; ++i) perm[order[i]] = i;
-    for (size_t k = 0; k < artic_sorted.size(); k += MG_ARTIC_I_N) artic_sorted[k] = perm[artic_sorted[k]];
-    for (size_t k = 0; k < artic_step.size(); k += MG_ARTIC_I_N) artic_step[k] = perm[artic_step[k]];
-    // chain groups whose stepped rows follow the blocked layout from one base
-    // slot and one DOF stride: the kernel computes them (MgArticArgs::aff)
-    for (ArticGroup& g : s->groups) {
-        g.aff = 0;
-        if (!(g.chain && g.nl >= 2 && g.nl <= 4) || g.step_count == 0) continue;
-        const int* r0 = artic_step.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
-        const int B = r0[0], D = r0[1];
-        const int DS = g.step_count > 1 ? r0[MG_ARTIC_I_N + 1] - D : 0;
-        bool ok = true;
-        for (int k = 0; k < g.step_count && ok; ++k) {
-            const int* r = r0 + (size_t)k * MG_ARTIC_I_N;
-            const int blk = k / 64, j = k % 64, cnt = std::min(64, g.step_count - blk * 64);
-            ok = r[0] == B + blk * 64 * g.nbody + j && r[3] == cnt && r[1] == D + k * DS;
-        }
-        if (ok) { g.aff = 1; g.aff_b0 = B; g.aff_d0 = D; g.aff_ds = DS; }
-    }
-    // coupled env rows: internal slots, grouped by articulation template (-1 first)
-    std::vector<int> env_flat;
-    s->env_groups.clear();
-    s->cenv_ctab_off.assign(env_rows.size(), -1);
-    s->cenv_ctab_n.assign(env_rows.size(), 0);
-    s->h_cenv_row.assign(env_rows.size(), 0);
-    // (and by lane width: an env of more than 16 links or velocity slots runs
-    // 64 lanes wide, mg_env.hip; the oracle decides per env the same way)
-    for (int t = -1; t < m->num_artic_tmpls; ++t)
-    for (int wide = 0; wide < 2; ++wide) {
-        EnvGroup g{};
-        g.tmpl = t;
-        g.wide = wide;
-        if (t >= 0) {
-            g.first_link = m->artic_tmpl_i[t * MG_ATMPL_I_N + 0];
-            g.nl = m->artic_tmpl_i[t * MG_ATMPL_I_N + 1];
-            g.ndof = m->artic_tmpl_i[t * MG_ATMPL_I_N + 2];
-            g.floating = m->artic_tmpl_i[t * MG_ATMPL_I_N + 3] ? 0 : 1;
-        }
-        g.offset = (int)env_flat.size() / MG_ENV_I_N;
-        for (size_t r = 0; r < env_rows.size(); ++r) {
-            if (env_tmpl[r] != t) continue;
-            const int slots = (t >= 0 ? g.ndof + 6 * g.floating : 0) + 6 * env_rows[r][2];
-            if ((g.nl > 16 || slots > 16) != (wide != 0)) continue;
-            std::array<int, MG_ENV_I_N> row = env_rows[r];
-            g.max_free = std::max(g.max_free, row[2]);
-            if (row[0] >= 0) row[0] = perm[row[0]];
-            for (int i = 0; i < row[2]; ++i) row[3 + i] = perm[row[3 + i]];
-            for (int i = 0; i < row[7]; ++i) row[8 + i] = perm[row[8 + i]];
-            env_flat.insert(env_flat.end(), row.begin(), row.end());
-            // k_env_np writes env j of the group at the group's base + j records
-            s->cenv_ctab_off[r] = (long long)g.offset * mg_env_ctab_floats() +
-                                  (long long)g.count * mg_env_ctab_record_floats(wide);
-            s->cenv_ctab_n[r] = mg_env_ctab_record_floats(wide);
-            s->h_cenv_row[r] = g.offset + g.count;
-            g.count++;
-        }
-        if (g.count > 0) s->env_groups.push_back(g);
-    }
-    s->n_coupled = (int)env_rows.size();
-    s->h_env_d0.assign(env_rows.size(), 0);
-    for (size_t r = 0; r < env_rows.size(); ++r) s->h_env_d0[r] = env_flat[r * MG_ENV_I_N + 1];
-    s->n_pile = (int)pile_rows.size();
-    for (auto& r : pile_rows)
-        for (int t = 0; t < r[4]; ++t) r[5 + t] = perm[r[5 + t]];
-    for (int& b : pile_body) b = perm[b];
-    for (int b = 0; b < nb; ++b)
-        if (m->body_kind[b] == MG_BODY_FREE && perm[b] < s->nf)
-            s->h_body_class[b] = perm[b] < s->nf_rigid ? ATTR_FREE : ATTR_ENV_FREE;
-    for (int slot : pile_body) s->h_body_class[order[slot]] = ATTR_PILE;
-    s->h_artic_step = artic_step;
-    std::vector<int> root_int(na), tmpl_int(nb);
-    for (int a = 0; a < na; ++a) root_int[a] = perm[m->actor_root_body[a]];
-    for (int i = 0; i < nb; ++i) tmpl_int[i] = m->body_tmpl[order[i]];
-    std::vector<float> st0((size_t)nb * MG_STATE_N), ms0((size_t)nb * MG_MASS_N);
-    for (int i = 0; i < nb; ++i) {
-        std::memcpy(&st0[(size_t)i * MG_STATE_N], m->body_state0 + (size_t)order[i] * MG_STATE_N, MG_STATE_N * sizeof(float));
-        std::memcpy(&ms0[(size_t)i * MG_MASS_N], m->body_mass + (size_t)order[i] * MG_MASS_N, MG_MASS_N * sizeof(float));
-    }
-
-    // device buffers
-    HIP_TRY(dalloc(&s->d_state, (size_t)nb * MG_STATE_N));
-    HIP_TRY(dalloc(&s->d_mass, (size_t)nb * MG_MASS_N));
-    HIP_TRY(dalloc(&s->d_body_tmpl, nb));
-    HIP_TRY(dalloc(&s->d_free_global, s->nf));
-    HIP_TRY(dalloc(&s->d_perm, nb));
-    HIP_TRY(dalloc(&s->d_tbf, (size_t)s->ntb * MG_TBODY_F_N));
-    HIP_TRY(dalloc(&s->d_tbi, (size_t)s->ntb * MG_TBODY_I_N));
-    HIP_TRY(dalloc(&s->d_trec, (size_t)s->ntb * MG_TREC_N));
-    HIP_TRY(dalloc(&s->d_shapes, (size_t)s->ns * MG_SHAPE_STRIDE));
-    HIP_TRY(dalloc(&s->d_hulls, (size_t)(m->hulls ? m->num_hull_floats : 0)));
-    s->nhull_floats = m->hulls ? m->num_hull_floats : 0;
-    HIP_TRY(dalloc(&s->d_actor_root, na));
-    HIP_TRY(dalloc(&s->d_actor_dof, na + 1));
-    HIP_TRY(dalloc(&s->d_cforce, (size_t)nb * 3));
-    HIP_TRY(dalloc(&s->d_ext, (size_t)nb * 6));
-    HIP_TRY(dalloc(&s->d_dof, (size_t)nd * 2));
-    HIP_TRY(dalloc(&s->d_dof_tgt, (size_t)nd * 3));
-    HIP_TRY(dalloc(&s->d_dof_props, (size_t)nd * MG_DOFPROP_N));
-    HIP_TRY(dalloc(&s->d_dof_frc, (size_t)nd * 2));
-    HIP_TRY(dalloc(&s->d_artic, artic_sorted.size()));
-    HIP_TRY(dalloc(&s->d_artic_step, artic_step.size()));
-    HIP_TRY(dalloc(&s->d_env, env_flat.size()));
-    HIP_TRY(dalloc(&s->d_pairs, pairs.size()));
-    HIP_TRY(dalloc(&s->d_link_f, (size_t)s->ntl * MG_LINK_F_N));
-    HIP_TRY(dalloc(&s->d_link_i, (size_t)s->ntl * MG_LINK_I_N));
-
-    auto h2d = [](void* d, const void* h, size_t bytes) -> hipError_t {
-        if (bytes == 0 || !h) return hipSuccess;
-        return hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
-    };
-    std::vector<float> st = to_soa(st0.data(), nb, MG_STATE_N);
-    std::vector<float> ms = to_soa(ms0.data(), nb, MG_MASS_N);
-    HIP_TRY(h2d(s->d_state, st.data(), st.size() * sizeof(float)));
-    HIP_TRY(h2d(s->d_mass, ms.data(), ms.size() * sizeof(float)));
-    HIP_TRY(h2d(s->d_body_tmpl, tmpl_int.data(), (size_t)nb * sizeof(int)));
-    HIP_TRY(h2d(s->d_free_global, free_ids.data(), free_ids.size() * sizeof(int)));
-    HIP_TRY(h2d(s->d_perm, perm.data(), (size_t)nb * sizeof(int)));
-    HIP_TRY(h2d(s->d_tbf, m->tmpl_body_f, (size_t)s->ntb * MG_TBODY_F_N * sizeof(float)));
-    HIP_TRY(h2d(s->d_tbi, m->tmpl_body_i, (size_t)s->ntb * MG_TBODY_I_N * sizeof(int)));
-    {
-        // compact template records of the single-shape kernel: template floats,
-        // then the first shape record (type -1: no shape)
-        std::vector<float> trec((size_t)s->ntb * MG_TREC_N, 0.0f);
-        for (int t = 0; t < s->ntb; ++t) {
-            float* r = &trec[(size_t)t * MG_TREC_N];
-            std::memcpy(r, m->tmpl_body_f + (size_t)t * MG_TBODY_F_N, MG_TBODY_F_N * sizeof(float));
-            const int s0 = m->tmpl_body_i[t * MG_TBODY_I_N + 0], sc = m->tmpl_body_i[t * MG_TBODY_I_N + 1];
-            if (sc > 0) {
-                const float* sr = m->shapes + (size_t)s0 * MG_SHAPE_STRIDE;
-                std::memcpy(r + MG_TBODY_F_N, sr, MG_SHAPE_STRIDE * sizeof(float));
-                // pad[0] of the copy: bounding radius of the shape about the body
-                // origin (k_rigid_step1 skips the candidates of a wave whose bodies
-                // all clear the ground by more than it); -1: unknown, never skipped
-                double ext = -1.0;
-                switch ((int)sr[0]) {
-                    case MG_SHAPE_SPHERE: ext = sr[1]; break;
-                    case MG_SHAPE_BOX: ext = std::sqrt((double)sr[1] * sr[1] + (double)sr[2] * sr[2] + (double)sr[3] * sr[3]); break;
-                    case MG_SHAPE_CAPSULE: ext = (double)sr[1] + sr[2]; break;
-                    case MG_SHAPE_CONVEX: ext = sr[1]; break;
-                    default: break;
-                }
-                const double po = std::sqrt((double)sr[4] * sr[4] + (double)sr[5] * sr[5] + (double)sr[6] * sr[6]);
-                r[MG_TBODY_F_N + 13] = (ext >= 0.0 && std::isfinite(ext + po)) ? (float)((ext + po) * (1.0 + 1e-6)) : -1.0f;
-            } else {
-                r[MG_TBODY_F_N] = -1.0f;
-            }
-        }
-        // one mass row per template when all its free bodies share it (the kernel
-        // then reads it from the record instead of 44 B per body)
-        std::vector<int> seen(s->ntb, 0), uniform(s->ntb, 1);
-        for (int b = 0; b < nb; ++b) {
-            if (m->body_kind[b] != MG_BODY_FREE) continue;
-            const int t = m->body_tmpl[b];
-            const float* mr = m->body_mass + (size_t)b * MG_MASS_N;
-            float* r = &trec[(size_t)t * MG_TREC_N];
-            if (!seen[t]) {
-                std::memcpy(r + MG_TREC_MASS, mr, MG_MASS_N * sizeof(float));
-                seen[t] = 1;
-            } else if (std::memcmp(r + MG_TREC_MASS, mr, MG_MASS_N * sizeof(float)) != 0) {
-                uniform[t] = 0;
-            }
-        }
-        for (int t = 0; t < s->ntb; ++t) trec[(size_t)t * MG_TREC_N + 5] = seen[t] && uniform[t] ? 1.0f : 0.0f;
-        HIP_TRY(h2d(s->d_trec, trec.data(), trec.size() * sizeof(float)));
-    }
-    HIP_TRY(h2d(s->d_shapes, m->shapes, (size_t)s->ns * MG_SHAPE_STRIDE * sizeof(float)));
-    if (m->hulls) HIP_TRY(h2d(s->d_hulls, m->hulls, (size_t)m->num_hull_floats * sizeof(float)));
-    {
-        std::vector<float> obb((size_t)std::max(s->ns, 1) * MG_OBB_N, 0.0f);
-        for (int k = 0; k < s->ns; ++k) shape_obb(m->shapes + (size_t)k * MG_SHAPE_STRIDE, m->hulls, &obb[(size_t)k * MG_OBB_N]);
-        HIP_TRY(dalloc(&s->d_shape_obb, obb.size()));
-        HIP_TRY(h2d(s->d_shape_obb, obb.data(), obb.size() * sizeof(float)));
-    }
-    HIP_TRY(h2d(s->d_actor_root, root_int.data(), (size_t)na * sizeof(int)));
-    {
-        std::vector<int> body_actor(nb, -1);
-        for (int a = 0; a < na; ++a) body_actor[m->actor_root_body[a]] = a;
-        HIP_TRY(dalloc(&s->d_body_actor, (size_t)std::max(nb, 1)));
-        HIP_TRY(h2d(s->d_body_actor, body_actor.data(), (size_t)nb * sizeof(int)));
-    }
-    // the per-slot indices of the free-body step packed into one record per slot
-    // (the same values as d_root_row, d_body_tmpl, d_slot_global, d_slot_actor)
-    std::vector<MgSlotRec> slot_rec((size_t)std::max(nb, 1), MgSlotRec{-1, 0, 0, -1});
-    {
-        // fusable root sets: every actor root is a single-shape free body of the
-        // free-body kernel (internal slots 0..nf1-1), and that kernel steps all
-        // free bodies (no multi-shape ones, no articulations, no coupled envs)
-        std::vector<int> row(nb, -1);
-        bool ok = s->nf1 == s->nf_rigid && s->nf_rigid == s->nf && s->nartic == 0 && s->n_coupled == 0 &&
-                  s->n_pile == 0 && na > 0;
-        for (int a = 0; a < na && ok; ++a) {
-            const int slot = root_int[a];
-            ok = slot >= 0 && slot < s->nf1 && row[slot] < 0;
-            if (ok) row[slot] = a;
-        }
-        s->roots_free = ok;
-        HIP_TRY(dalloc(&s->d_root_row, (size_t)std::max(nb, 1)));
-        HIP_TRY(h2d(s->d_root_row, row.data(), (size_t)nb * sizeof(int)));
-        for (int i = 0; i < nb; ++i) slot_rec[i].root_row = row[i];
-    }
-    {
-        // rows the step kernels write with the refresh fused into them
-        // (MG_FUSE_STEP_OUT): internal slot -> rigid-body row / actor row
-        std::vector<int> slot_actor(nb, -1);
-        for (int a = 0; a < na; ++a) slot_actor[root_int[a]] = a;
-        // the env of each actor root's slot (the contact list's env column)
-        s->h_slot_env.assign((size_t)std::max(nb, 1), 0);
-        if (m->actor_coll)
-            for (int a = 0; a < na; ++a) s->h_slot_env[root_int[a]] = m->actor_coll[(size_t)a * MG_ACOLL_N + 0];
-        HIP_TRY(dalloc(&s->d_slot_global, (size_t)std::max(nb, 1)));
-        HIP_TRY(h2d(s->d_slot_global, order.data(), (size_t)nb * sizeof(int)));
-        HIP_TRY(dalloc(&s->d_slot_actor, (size_t)std::max(nb, 1)));
-        HIP_TRY(h2d(s->d_slot_actor, slot_actor.data(), (size_t)nb * sizeof(int)));
-        for (int i = 0; i < nb; ++i) {
-            slot_rec[i].body_tmpl = tmpl_int[i];
-            slot_rec[i].out_body = order[i];
-            slot_rec[i].out_root_row = slot_actor[i];
-        }
-        HIP_TRY(dalloc(&s->d_slot_rec, slot_rec.size()));
-        HIP_TRY(h2d(s->d_slot_rec, slot_rec.data(), (size_t)nb * sizeof(MgSlotRec)));
-        // chain groups whose fused-refresh rows are affine in the instance
-        for (ArticGroup& g : s->groups) {
-            g.out_aff = 0;
-            if (!g.aff) continue;
-            const int* r0 = artic_step.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
-            const int G0 = order[r0[0]], A0 = slot_actor[r0[0]];
-            bool ok = A0 >= 0;
-            for (int k = 0; k < g.step_count && ok; ++k) {
-                const int* r = r0 + (size_t)k * MG_ARTIC_I_N;
-                ok = slot_actor[r[0]] == A0 + k;
-                for (int l = 0; l < g.nl && ok; ++l) ok = order[r[0] + l * r[3]] == G0 + k * g.nl + l;
-            }
-            if (ok) { g.out_aff = 1; g.out_g0 = G0; g.out_r0 = A0; }
-        }
-        long long covered = s->nf1 == s->nf_rigid && s->nf_rigid == s->nf ? s->nf1 : -1;
-        for (const ArticGroup& g : s->groups) {
-            if (covered < 0) break;
-            if (g.count == 0) continue;
-            if (!(g.chain && g.nl >= 2 && g.nl <= 4) || g.step_count != g.count) covered = -1;
-            else covered += (long long)g.step_count * g.nbody;
-        }
-        s->step_out_ok = s->n_coupled == 0 && s->n_pile == 0 && nb > 0 && covered == nb;
-    }
-    HIP_TRY(h2d(s->d_actor_dof, m->actor_dof, (size_t)(na + 1) * sizeof(int)));
-    HIP_TRY(hipMemset(s->d_cforce, 0, (size_t)nb * 3 * sizeof(float)));
-    HIP_TRY(hipMemset(s->d_dof_frc, 0, std::max<size_t>((size_t)nd * 2, 1) * sizeof(float)));
-    s->h_actor_dof.assign(m->actor_dof, m->actor_dof + (na > 0 ? na + 1 : 0));
-    s->dof_frc_n = 0;
-    HIP_TRY(hipMemset(s->d_ext, 0, (size_t)nb * 6 * sizeof(float)));
-    if (nd > 0) {
-        std::vector<float> ds = to_soa(m->dof_state0, nd, 2);
-        HIP_TRY(h2d(s->d_dof, ds.data(), ds.size() * sizeof(float)));
-        HIP_TRY(hipMemset(s->d_dof_tgt, 0, (size_t)nd * 3 * sizeof(float)));
-        std::vector<float> dp = to_soa(m->dof_props, nd, MG_DOFPROP_N);
-        HIP_TRY(h2d(s->d_dof_props, dp.data(), dp.size() * sizeof(float)));
-    }
-    for (ArticGroup& g : s->groups)
-        if (g.uni_mass) chain_uni_dof(m->dof_props, g);
-    HIP_TRY(dalloc(&s->d_chain_uni, std::max<size_t>(s->groups.size(), 1) * MG_CHAIN_UNI_N));
-    HIP_TRY(chain_uni_upload(s));
+    // bodies, templates, shapes
+    HIP_TRY(M.d_state.upload(L.state0));
+    HIP_TRY(M.d_mass.upload(L.mass0));
+    HIP_TRY(M.d_body_tmpl.upload(L.tmpl_int));
+    HIP_TRY(M.d_free_global.upload(L.order.data(), (size_t)L.nf));
+    HIP_TRY(M.d_perm.upload(L.perm));
+    HIP_TRY(M.d_tbf.upload(m->tmpl_body_f, (size_t)L.ntb * MG_TBODY_F_N));
+    HIP_TRY(M.d_tbi.upload(m->tmpl_body_i, (size_t)L.ntb * MG_TBODY_I_N));
+    HIP_TRY(M.d_trec.upload(L.trec));
+    HIP_TRY(M.d_shapes.upload(m->shapes, (size_t)L.ns * MG_SHAPE_STRIDE));
+    HIP_TRY(M.d_hulls.upload(m->hulls, (size_t)L.nhull_floats));
+    HIP_TRY(M.d_shape_obb.upload(L.shape_obb));
+    // actors and the per-slot index tables
+    HIP_TRY(M.d_actor_root.upload(L.root_int));
+    HIP_TRY(M.d_body_actor.upload(L.body_actor));
+    HIP_TRY(M.d_root_row.upload(L.root_row));
+    HIP_TRY(M.d_slot_global.upload(L.order));
+    HIP_TRY(M.d_slot_actor.upload(L.slot_actor));
+    HIP_TRY(M.d_slot_rec.upload(reinterpret_cast<const MgSlotRec*>(L.slot_rec.data()), (size_t)nb));
+    HIP_TRY(M.d_actor_dof.upload(m->actor_dof, (size_t)na + 1));
+    HIP_TRY(M.d_cforce.zero((size_t)nb * 3));
+    HIP_TRY(M.d_ext.zero((size_t)nb * 6));
+    // DOFs
+    HIP_TRY(M.d_dof.upload(to_soa(m->dof_state0, nd, 2)));
+    HIP_TRY(M.d_dof_tgt.zero((size_t)nd * 3));
+    HIP_TRY(M.d_dof_props.upload(to_soa(m->dof_props, nd, MG_DOFPROP_N)));
+    HIP_TRY(M.d_dof_frc.zero((size_t)nd * 2));
+    // articulations
+    HIP_TRY(M.d_chain_uni.alloc(std::max<size_t>(M.groups.size(), 1) * MG_CHAIN_UNI_N));
+    HIP_TRY(chain_uni_upload(&M));
     if (nd > 0) {   // joint friction: which kernels step the DOFs with friction > 0
         JfrPlan pl;
-        if (int rc_ = jfr_plan(s, m->dof_props, pl)) return rc_;
-        if (int rc_ = jfr_commit(s, pl)) return rc_;
+        if (int rc_ = jfr_plan(&M, m->dof_props, pl)) return rc_;
+        if (int rc_ = jfr_commit(&M, pl)) return rc_;
     }
-    HIP_TRY(h2d(s->d_artic, artic_sorted.data(), artic_sorted.size() * sizeof(int)));
-    HIP_TRY(h2d(s->d_artic_step, artic_step.data(), artic_step.size() * sizeof(int)));
-    HIP_TRY(h2d(s->d_env, env_flat.data(), env_flat.size() * sizeof(int)));
-    HIP_TRY(h2d(s->d_pairs, pairs.data(), pairs.size() * sizeof(int)));
-    if (s->n_pile > 0) {
-        std::vector<int> flat;
-        for (const auto& r : pile_rows) flat.insert(flat.end(), r.begin(), r.end());
-        HIP_TRY(dalloc(&s->d_pile_i, flat.size()));
-        HIP_TRY(h2d(s->d_pile_i, flat.data(), flat.size() * sizeof(int)));
-        HIP_TRY(dalloc(&s->d_pile_body, pile_body.size()));
-        HIP_TRY(h2d(s->d_pile_body, pile_body.data(), pile_body.size() * sizeof(int)));
-        HIP_TRY(dalloc(&s->d_pile_pairs, std::max<size_t>(pile_pairs.size(), 1)));
-        if (!pile_pairs.empty())
-            HIP_TRY(h2d(s->d_pile_pairs, pile_pairs.data(), pile_pairs.size() * sizeof(unsigned)));
-        HIP_TRY(dalloc(&s->d_pile_slots, std::max<size_t>(pile_slots.size(), 2)));
-        if (!pile_slots.empty()) HIP_TRY(h2d(s->d_pile_slots, pile_slots.data(), pile_slots.size() * sizeof(int)));
+    HIP_TRY(M.d_artic.upload(L.artic_sorted));
+    HIP_TRY(M.d_artic_step.upload(L.artic_step));
+    HIP_TRY(M.d_link_f.upload(m->tmpl_link_f, (size_t)L.ntl * MG_LINK_F_N));
+    HIP_TRY(M.d_link_i.upload(m->tmpl_link_i, (size_t)L.ntl * MG_LINK_I_N));
+    // coupled envs: rows, pairs, friction patches (none yet: every pair starts
+    // without anchors), the step's per-env records between its launches
+    HIP_TRY(M.d_env.upload(L.env_flat));
+    HIP_TRY(M.d_pairs.upload(L.pairs));
+    const size_t nc = (size_t)std::max(L.n_coupled, 1);
+    HIP_TRY(M.d_fpatch.zero(std::max<size_t>(L.pairs.size() / 4, 1) * MG_FP_N));
+    HIP_TRY(M.d_fp_mask.zero(nc * MG_FP_W));
+    HIP_TRY(M.d_env_carry.alloc(nc * mg_env_carry_floats()));
+    HIP_TRY(M.d_env_ctab.alloc(nc * mg_env_ctab_floats()));
+    HIP_TRY(M.d_gpatch.zero((size_t)std::max(L.nf1, 1) * MG_FP_N));   // no ground patch yet
+    if (L.n_pile > 0) {
+        HIP_TRY(M.d_pile_i.upload(L.pile_rows));
+        HIP_TRY(M.d_pile_body.upload(L.pile_body));
+        HIP_TRY(M.d_pile_pairs.upload(L.pile_pairs));
+        HIP_TRY(M.d_pile_slots.upload(L.pile_slots, 2));
     }
-    {   // no friction patch yet: every pair starts without anchors
-        const size_t np = std::max<size_t>(pairs.size() / 4, 1), nm = (size_t)std::max(s->n_coupled, 1) * MG_FP_W;
-        HIP_TRY(dalloc(&s->d_fpatch, np * MG_FP_N));
-        HIP_TRY(dalloc(&s->d_fp_mask, nm));
-        HIP_TRY(hipMemset(s->d_fpatch, 0, np * MG_FP_N * sizeof(float)));
-        HIP_TRY(hipMemset(s->d_fp_mask, 0, nm * sizeof(unsigned)));
-        // the coupled step's per-env records between its launches (mg_env.hip)
-        const size_t nc = (size_t)std::max(s->n_coupled, 1);
-        HIP_TRY(dalloc(&s->d_env_carry, nc * mg_env_carry_floats()));
-        HIP_TRY(dalloc(&s->d_env_ctab, nc * mg_env_ctab_floats()));
-        const size_t ng = (size_t)std::max(s->nf1, 1) * MG_FP_N;   // no ground patch yet
-        HIP_TRY(dalloc(&s->d_gpatch, ng));
-        HIP_TRY(hipMemset(s->d_gpatch, 0, ng * sizeof(float)));
-    }
-    HIP_TRY(h2d(s->d_link_f, m->tmpl_link_f, (size_t)s->ntl * MG_LINK_F_N * sizeof(float)));
-    HIP_TRY(h2d(s->d_link_i, m->tmpl_link_i, (size_t)s->ntl * MG_LINK_I_N * sizeof(int)));
     HIP_TRY(hipDeviceSynchronize());
-    s->h_perm = perm;
-    s->h_body_tmpl.assign(m->body_tmpl, m->body_tmpl + nb);
-    s->h_tbi.assign(m->tmpl_body_i, m->tmpl_body_i + (size_t)s->ntb * MG_TBODY_I_N);
+    // ---- commit (nothing below fails); the initial state went to the device
+    std::vector<float>().swap(L.state0);
+    std::vector<float>().swap(L.mass0);
+    static_cast<Model&>(*s) = std::move(M);
+    s->dof_frc_n = 0;
     s->uploaded = true;
     return MG_OK;
 }
@@ -1601,7 +879,7 @@ static void fused_targets(mg_sim* s, const float*& tp, const float*& tv, const f
         *out[k] = nullptr;
         if (s->pend_tgt[k]) {
             *in[k] = s->pend_tgt[k];
-            *out[k] = s->d_dof_tgt + (size_t)k * s->nd;
+            *out[k] = s->d_dof_tgt + (size_t)k * s->layout.nd;
         }
     }
 }
@@ -1609,7 +887,7 @@ static void fused_targets(mg_sim* s, const float*& tp, const float*& tv, const f
 // the force sensor kernels' argument block (mg_sensor.hip)
 static MgSensorArgs sensor_args(const mg_sim* s, const MgStep& P) {
     MgSensorArgs A{};
-    A.n = s->n_sens; A.n_art = s->n_sart; A.nb = s->nb; A.nd = s->nd; A.nhb = s->sens_nhb;
+    A.n = s->n_sens; A.n_art = s->n_sart; A.nb = s->layout.nb; A.nd = s->layout.nd; A.nhb = s->sens_nhb;
     A.sens_i = s->d_sens_i; A.sens_f = s->d_sens_f; A.sart_i = s->d_sart_i;
     A.perm = s->d_perm; A.link_i = s->d_link_i;
     A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
@@ -1673,7 +951,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         mg_timer = &timer;
     }
     // the refresh fused into the step (MG_FUSE_STEP_OUT): every body's rows are
-    // written by the kernel that steps it (s->step_out_ok), into the bound
+    // written by the kernel that steps it (s->layout.step_out_ok), into the bound
     // tensors (each one optional)
     if (s->n_sens > 0) {
         // force sensors: which articulations begin the frame with a state set
@@ -1682,17 +960,17 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         HIP_TRY(mg_launch_sensor_mark(sensor_args(s, P), st));
     }
     const unsigned long long step_cid = capture_id(st);
-    const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->step_out_ok &&
+    const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->layout.step_out_ok &&
                           s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 &&
                           (s->bind_root || s->bind_rb || s->bind_dof);
     // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
     // write into the library's own buffer, so no caller-visible tensor changes
     float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && s->step_out_ok && s->attrs.empty() && !s->crep_on &&
+    const bool host_out = !step_out && ho_base && s->layout.step_out_ok && s->attrs.empty() && !s->crep_on &&
                           s->jfr_ndof == 0 && step_cid == 0;
     float* ho_root = host_out ? ho_base : nullptr;
-    float* ho_rb = host_out ? ho_base + (size_t)s->na * MG_STATE_N : nullptr;
-    float* ho_dof = host_out && s->nd ? ho_base + (size_t)(s->na + s->nb) * MG_STATE_N : nullptr;
+    float* ho_rb = host_out ? ho_base + (size_t)s->layout.na * MG_STATE_N : nullptr;
+    float* ho_dof = host_out && s->layout.nd ? ho_base + (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N : nullptr;
     for (size_t gi = 0; gi < s->groups.size(); ++gi) {
         const ArticGroup& g = s->groups[gi];
         if (g.step_count == 0) continue;
@@ -1700,7 +978,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         // the DOF part's validity is a flag in the block (MG_CHAIN_UNI_DOFOK), not
         // a launch choice: a captured launch follows later set_dof_props
         A.uni = g.uni_mass ? s->d_chain_uni + gi * MG_CHAIN_UNI_N : nullptr;
-        A.na = g.step_count; A.nb = s->nb; A.nd = s->nd;
+        A.na = g.step_count; A.nb = s->layout.nb; A.nd = s->layout.nd;
         A.artic_i = s->d_artic_step + (size_t)g.step_offset * MG_ARTIC_I_N;
         A.aff = g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
         A.out_aff = g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
@@ -1708,14 +986,14 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.link_f = s->d_link_f + (size_t)g.first_link * MG_LINK_F_N;
         A.link_i = s->d_link_i + (size_t)g.first_link * MG_LINK_I_N;
         A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
-        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->nd;
-        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->nd;
+        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
+        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
         fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
         A.dof_props = s->d_dof_props;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
         A.dof_frc = s->dof_frc_n > 0 ? s->d_dof_frc : nullptr;
-        if (step_out || host_out) {   // chain groups only (s->step_out_ok)
+        if (step_out || host_out) {   // chain groups only (s->layout.step_out_ok)
             A.out_rb = step_out ? s->bind_rb : ho_rb;
             A.out_root = step_out ? s->bind_root : ho_root;
             A.out_dof = step_out ? s->bind_dof : ho_dof;
@@ -1765,7 +1043,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     }
     for (const EnvGroup& g : s->env_groups) {
         MgEnvArgs A{};
-        A.ne = g.count; A.nb = s->nb; A.nd = s->nd;
+        A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
         A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
         A.pairs = s->d_pairs;
         A.fpatch = s->d_fpatch;
@@ -1781,10 +1059,10 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
         A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
         A.shape_obb = s->d_shape_obb;
-        A.nhull = s->nhull_floats;
-        A.nshape = s->ns;
-        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->nd;
-        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->nd;
+        A.nhull = s->layout.nhull_floats;
+        A.nshape = s->layout.ns;
+        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
+        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
         fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
         A.dof_props = s->d_dof_props;
         A.ext = s->ext_pending ? s->d_ext : nullptr;
@@ -1799,7 +1077,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.crep = s->d_crep_cenv + g.offset;
             A.crep_n = s->d_crep_cenv_n + g.offset;
             A.crep_body = s->d_slot_global;
-            A.crep_stride = std::max(s->n_coupled, 1);
+            A.crep_stride = std::max(s->layout.n_coupled, 1);
             A.dof_frc = s->d_dof_frc;
         }
         if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) {
@@ -1819,9 +1097,9 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         hipError_t e = mg_launch_env_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
     }
-    if (s->n_pile > 0) {
+    if (s->layout.n_pile > 0) {
         MgPileArgs A{};
-        A.ne = s->n_pile; A.nb = s->nb;
+        A.ne = s->layout.n_pile; A.nb = s->layout.nb;
         A.pile_i = s->d_pile_i; A.pile_body = s->d_pile_body; A.pairs = s->d_pile_pairs; A.slots = s->d_pile_slots;
         A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
         A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
@@ -1835,15 +1113,15 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         hipError_t e = mg_launch_pile_step(P, A, st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
     }
-    if (s->nf_rigid > 0) {
+    if (s->layout.nf_rigid > 0) {
         MgRigidArgs A{};
-        A.nf = s->nf_rigid; A.nf1 = s->nf1; A.nb = s->nb; A.free_ids = nullptr;   // internal slots 0..nf-1
+        A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
         A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
         A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
-        A.trec = s->d_trec; A.ntb = s->ntb;
+        A.trec = s->d_trec; A.ntb = s->layout.ntb;
         A.slot_rec = s->d_slot_rec;
         A.gpatch = s->d_gpatch;
-        A.gstride = std::max(s->nf1, 1);
+        A.gstride = std::max(s->layout.nf1, 1);
         A.ext = s->ext_pending ? s->d_ext : nullptr;
         A.cforce = s->d_cforce;
         if (s->n_attr_free > 0) {
@@ -1854,7 +1132,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.crep = s->d_crep_free;
             A.crep_n = s->d_crep_free_n;
             A.crep_body = s->d_slot_global;
-            A.crep_stride = std::max(s->nf_rigid, 1);
+            A.crep_stride = std::max(s->layout.nf_rigid, 1);
         }
         bool reads_root_in = false;
         if (s->pend_root) {   // the deferred root set, read by the step kernel
@@ -1896,26 +1174,26 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     if (s->crep_on) {
         // the contact list of this frame: the staging records packed in owner order
         MgContactArgs C{};
-        C.fam[0].n = s->nf_rigid;
+        C.fam[0].n = s->layout.nf_rigid;
         C.fam[0].cap = MG_CREP_FREE_CAP;
-        C.fam[0].stride = std::max(s->nf_rigid, 1);
+        C.fam[0].stride = std::max(s->layout.nf_rigid, 1);
         C.fam[0].stage = s->d_crep_free;
         C.fam[0].count = s->d_crep_free_n;
         C.fam[0].env = s->d_crep_env;
-        C.fam[1].n = s->n_coupled;
+        C.fam[1].n = s->layout.n_coupled;
         C.fam[1].cap = 2 * MG_ENV_MAXCT_WIDE;
-        C.fam[1].stride = std::max(s->n_coupled, 1);
+        C.fam[1].stride = std::max(s->layout.n_coupled, 1);
         C.fam[1].stage = s->d_crep_cenv;
         C.fam[1].count = s->d_crep_cenv_n;
-        C.fam[1].env = s->d_crep_env + s->nf_rigid;
+        C.fam[1].env = s->d_crep_env + s->layout.nf_rigid;
         C.fam[1].col = s->d_crep_col;
-        C.fam[2].n = s->n_pile;
+        C.fam[2].n = s->layout.n_pile;
         C.fam[2].cap = MG_PILE_MAXPT;
-        C.fam[2].stride = std::max(s->n_pile, 1);
+        C.fam[2].stride = std::max(s->layout.n_pile, 1);
         C.fam[2].stage = s->d_crep_pile;
         C.fam[2].count = s->d_crep_pile_n;
-        C.fam[2].env = s->d_crep_env + s->nf_rigid + s->n_coupled;
-        C.n_own = s->nf_rigid + s->n_coupled + s->n_pile;
+        C.fam[2].env = s->d_crep_env + s->layout.nf_rigid + s->layout.n_coupled;
+        C.n_own = s->layout.nf_rigid + s->layout.n_coupled + s->layout.n_pile;
         C.nblk = (C.n_own + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK;
         C.blk_sum = s->d_crep_blk;
         C.out = s->d_crep_out;
@@ -1928,7 +1206,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // the force sensors' readings, before the applied wrenches are cleared
     if (s->n_sens > 0) HIP_TRY(mg_launch_force_sensor(sensor_args(s, P), st));
     if (s->ext_pending) {
-        HIP_TRY(hipMemsetAsync(s->d_ext, 0, (size_t)s->nb * 6 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(s->d_ext, 0, (size_t)s->layout.nb * 6 * sizeof(float), st));
         s->ext_pending = false;
     }
     mg_timer = nullptr;
@@ -1967,16 +1245,15 @@ int32_t mg_fetch_host_state(mg_sim* s, float* dst, int32_t parts, void* stream) 
     if (int rc_ = flush_root(s, st)) return rc_;
     // [na][13] roots, [nb][13] bodies, [nd][2] DOFs, [nb][3] contact forces; the
     // parts asked for are gathered and the span covering them copied at once
-    const size_t off[5] = {0, (size_t)s->na * MG_STATE_N, (size_t)(s->na + s->nb) * MG_STATE_N,
-                           (size_t)(s->na + s->nb) * MG_STATE_N + (size_t)s->nd * 2,
-                           (size_t)(s->na + s->nb) * MG_STATE_N + (size_t)s->nd * 2 + (size_t)s->nb * 3};
+    const size_t off[5] = {0, (size_t)s->layout.na * MG_STATE_N, (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N,
+                           (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N + (size_t)s->layout.nd * 2,
+                           (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N + (size_t)s->layout.nd * 2 + (size_t)s->layout.nb * 3};
     // zero-copy when dst is the sim's own mapped stage (mg_host_stage): the parts
     // the last simulate wrote are already there, the others are gathered into it
     const bool alias = s->h_stage && dst == s->h_stage && s->h_stage_n >= off[4];
     if (!alias && s->host_out_n < off[4]) {   // the output stage (simulate writes into it from now on)
-        if (s->d_host_out) (void)hipFree(s->d_host_out);
-        s->d_host_out = nullptr;
-        HIP_TRY(dalloc(&s->d_host_out, std::max<size_t>(off[4], 1)));
+        s->host_out_n = 0;
+        HIP_TRY(s->d_host_out.alloc(off[4]));
         s->host_out_n = off[4];
         if (s->ho_written && !s->ho_alias) s->ho_written = nullptr;
     }
@@ -1991,12 +1268,12 @@ int32_t mg_fetch_host_state(mg_sim* s, float* dst, int32_t parts, void* stream) 
         float* d = base + off[k];
         // parts the last simulate wrote there, with no state change since: no gather
         if (k == 0 && !(fresh && s->ho_root_gen == s->state_gen))
-            HIP_TRY(mg_launch_gather_rows(s->d_state, s->nb, MG_STATE_N, s->d_actor_root, s->na, d, st));
+            HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_actor_root, s->layout.na, d, st));
         if (k == 1 && !(fresh && s->ho_rb_gen == s->state_gen))
-            HIP_TRY(mg_launch_gather_rows(s->d_state, s->nb, MG_STATE_N, s->d_perm, s->nb, d, st));
+            HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, d, st));
         if (k == 2 && !(fresh && s->ho_dof_gen == s->dof_sgen))
-            HIP_TRY(mg_launch_gather_rows(s->d_dof, s->nd, 2, nullptr, s->nd, d, st));
-        if (k == 3) HIP_TRY(mg_launch_gather_rows(s->d_cforce, s->nb, 3, s->d_perm, s->nb, d, st));
+            HIP_TRY(mg_launch_gather_rows(s->d_dof, s->layout.nd, 2, nullptr, s->layout.nd, d, st));
+        if (k == 3) HIP_TRY(mg_launch_gather_rows(s->d_cforce, s->layout.nb, 3, s->d_perm, s->layout.nb, d, st));
     }
     if (lo >= 0 && !alias)
         HIP_TRY(hipMemcpyAsync(dst + off[lo], s->d_host_out + off[lo], (off[hi + 1] - off[lo]) * sizeof(float),
@@ -2038,17 +1315,17 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
         return fail(MG_ERR_STATE, "attractor table changed after the step was captured into a graph (the replays keep "
                     "the old launches); call it before the capture, or after an eager simulate");
     HIP_TRY(hipSetDevice(s->device));
-    std::vector<int> idx((size_t)std::max(s->nb, 1), -1);   // internal slot -> record
+    std::vector<int> idx((size_t)std::max(s->layout.nb, 1), -1);   // internal slot -> record
     for (int i = 0; i < n; ++i) {
         const mg_attractor& a = host[i];
-        if (a.body < 0 || a.body >= s->nb) return fail(MG_ERR_ARG, "attractor %d: body %d out of range", i, a.body);
+        if (a.body < 0 || a.body >= s->layout.nb) return fail(MG_ERR_ARG, "attractor %d: body %d out of range", i, a.body);
         if (!(std::isfinite(a.stiffness) && a.stiffness >= 0.0f && std::isfinite(a.damping) && a.damping >= 0.0f))
             return fail(MG_ERR_ARG, "attractor %d: stiffness and damping must be finite and non-negative", i);
         bool fin = true;
         for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(a.offset_p[k]) && std::isfinite(a.target_p[k]);
         for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(a.offset_q[k]) && std::isfinite(a.target_q[k]);
         if (!fin) return fail(MG_ERR_ARG, "attractor %d: offset and target must be finite", i);
-        const int slot = s->h_perm[a.body];
+        const int slot = s->layout.perm[a.body];
         if (idx[slot] >= 0)
             return fail(MG_ERR_UNSUPPORTED, "attractor %d: body %d already owns attractor %d (one attractor per body)",
                         i, a.body, idx[slot]);
@@ -2062,10 +1339,10 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     for (int i = 0; i < n; ++i) {
         const int b = host[i].body;
         const char* why = nullptr;
-        switch (s->h_body_class[b]) {
+        switch (s->layout.body_class[b]) {
             case ATTR_FREE: nfree++; break;
             case ATTR_ENV_LINK: nenv++; break;
-            case ATTR_LINK: nartic++; owns[s->h_body_grp[b]][s->h_body_inst[b]] = 1; break;
+            case ATTR_LINK: nartic++; owns[s->layout.body_grp[b]][s->layout.body_inst[b]] = 1; break;
             case ATTR_ENV_FREE: why = "a free body of a coupled env"; break;
             case ATTR_PILE: why = "a body of a pile env"; break;
             default: why = "not a dynamic body"; break;
@@ -2082,52 +1359,39 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     std::vector<int> split;
     std::vector<std::pair<int, int>> counts(s->groups.size(), {0, 0});   // plain, owners
     if (nartic > 0) {
-        split.resize(s->h_artic_step.size());
+        split.resize(s->layout.artic_step.size());
         for (size_t gi = 0; gi < s->groups.size(); ++gi) {
             const ArticGroup& g = s->groups[gi];
             int* dst = split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
             for (int pass = 0; pass < 2; ++pass)
                 for (int k = 0; k < g.step_count; ++k) {
                     if ((owns[gi][k] != 0) != (pass == 1)) continue;
-                    std::memcpy(dst, s->h_artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
+                    std::memcpy(dst, s->layout.artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
                                 MG_ARTIC_I_N * sizeof(int));
                     dst += MG_ARTIC_I_N;
                     (pass ? counts[gi].second : counts[gi].first)++;
                 }
         }
     }
-    struct Fresh {   // freed unless committed
-        int* idx = nullptr;
-        int* split = nullptr;
-        float* attr = nullptr;
-        float* host = nullptr;
-        ~Fresh() {
-            if (idx) (void)hipFree(idx);
-            if (split) (void)hipFree(split);
-            if (attr) (void)hipFree(attr);
-            if (host) (void)hipHostFree(host);
-        }
-    } fresh;
-    HIP_TRY(dalloc(&fresh.idx, idx.size()));
-    HIP_TRY(hipMemcpy(fresh.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (!split.empty()) {
-        HIP_TRY(dalloc(&fresh.split, split.size()));
-        HIP_TRY(hipMemcpy(fresh.split, split.data(), split.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    DevBuf<int> d_idx, d_split;   // freed unless committed
+    DevBuf<float> d_attr;
+    HostBuf<float> h_attr;
+    HIP_TRY(d_idx.upload(idx));
+    if (!split.empty()) HIP_TRY(d_split.upload(split));
     if (n > 0) {
-        HIP_TRY(dalloc(&fresh.attr, (size_t)n * MG_ATTR_N));
-        HIP_TRY(hipHostMalloc((void**)&fresh.host, (size_t)n * MG_ATTR_N * sizeof(float), hipHostMallocDefault));
-        for (int i = 0; i < n; ++i) attr_record(host[i], fresh.host + (size_t)i * MG_ATTR_N);
+        HIP_TRY(d_attr.alloc((size_t)n * MG_ATTR_N));
+        HIP_TRY(h_attr.alloc((size_t)n * MG_ATTR_N, false));
+        for (int i = 0; i < n; ++i) attr_record(host[i], h_attr + (size_t)i * MG_ATTR_N);
     }
     if (!s->attr_ev) HIP_TRY(hipEventCreateWithFlags(&s->attr_ev, hipEventDisableTiming));
     // no step may still read the buffers this replaces
     HIP_TRY(hipDeviceSynchronize());
     // ---- commit (nothing below fails)
     s->attr_ev_pending = false;
-    std::swap(s->d_attr_idx, fresh.idx);
-    std::swap(s->d_artic_split, fresh.split);
-    std::swap(s->d_attr, fresh.attr);
-    std::swap(s->h_attr, fresh.host);
+    s->d_attr_idx = std::move(d_idx);
+    s->d_artic_split = std::move(d_split);
+    s->d_attr = std::move(d_attr);
+    s->h_attr = std::move(h_attr);
     for (size_t gi = 0; gi < s->groups.size(); ++gi) {
         s->groups[gi].plain_count = counts[gi].first;
         s->groups[gi].attr_count = counts[gi].second;
@@ -2171,30 +1435,27 @@ float* mg_host_stage(mg_sim* s, int64_t nfloat) {
     if (hipSetDevice(s->device) != hipSuccess) { fail(MG_ERR_DEVICE, "hipSetDevice failed"); return nullptr; }
     if (s->h_stage) {
         (void)hipDeviceSynchronize();
-        (void)hipHostFree(s->h_stage);
-        s->h_stage = nullptr;
+        s->h_stage.reset();
         s->d_stage_alias = nullptr;
         s->h_stage_n = 0;
         s->ho_alias = false;
         s->ho_written = nullptr;
     }
-    float* h = nullptr;
-    if (hipHostMalloc((void**)&h, (size_t)nfloat * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent) !=
-        hipSuccess) {
+    HostBuf<float> h;
+    if (h.alloc((size_t)nfloat, true) != hipSuccess) {
         fail(MG_ERR_DEVICE, "hipHostMalloc of the host stage failed");
         return nullptr;
     }
     float* d = nullptr;
     if (hipHostGetDevicePointer((void**)&d, h, 0) != hipSuccess || !d) {
-        (void)hipHostFree(h);
         fail(MG_ERR_DEVICE, "hipHostGetDevicePointer of the host stage failed");
         return nullptr;
     }
     std::memset(h, 0, (size_t)nfloat * sizeof(float));
-    s->h_stage = h;
+    s->h_stage = std::move(h);
     s->d_stage_alias = d;
     s->h_stage_n = (size_t)nfloat;
-    return h;
+    return s->h_stage;
 }
 
 int32_t mg_set_fusion(mg_sim* s, int32_t flags) {
@@ -2228,7 +1489,7 @@ int32_t mg_discard_pending_sets(mg_sim* s) {
 }
 
 int32_t mg_step_out_supported(mg_sim* s) {
-    return s && s->uploaded && s->step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 ? 1 : 0;
+    return s && s->uploaded && s->layout.step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 ? 1 : 0;
 }
 
 int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
@@ -2302,12 +1563,12 @@ int32_t mg_step_untimed_launches(mg_sim* s, int32_t n) {
 // group's base and record size are the library's, so callers hard-code neither
 int32_t mg_debug_copy_env_ctab(mg_sim* s, int32_t k, float* dst, int32_t cap) {
     if (!s || !s->uploaded || !s->d_env_ctab || !dst) return fail(MG_ERR_ARG, "bad arguments");
-    if (k < 0 || k >= (int32_t)s->cenv_ctab_off.size()) return fail(MG_ERR_ARG, "no such coupled env");
-    const int32_t n = s->cenv_ctab_n[k];
+    if (k < 0 || k >= (int32_t)s->layout.cenv_ctab_off.size()) return fail(MG_ERR_ARG, "no such coupled env");
+    const int32_t n = s->layout.cenv_ctab_n[k];
     if (cap < n) return fail(MG_ERR_ARG, "dst holds fewer floats than the env's contact table");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dst, s->d_env_ctab + s->cenv_ctab_off[k], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dst, s->d_env_ctab + s->layout.cenv_ctab_off[k], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return n;
 }
 
@@ -2320,10 +1581,57 @@ int32_t mg_debug_artic_groups(mg_sim* s, int32_t* out, int32_t cap) {
         const ArticGroup& g = s->groups[i];
         int32_t* r = out + (size_t)i * MG_DEBUG_GROUP_N;
         r[0] = g.nl; r[1] = g.step_count; r[2] = g.chain; r[3] = g.uni_mass ? 1 : 0;
-        r[4] = g.uni_dof ? 1 : 0; r[5] = g.aff; r[6] = g.out_aff; r[7] = s->step_out_ok ? 1 : 0;
+        r[4] = g.uni_dof ? 1 : 0; r[5] = g.aff; r[6] = g.out_aff; r[7] = s->layout.step_out_ok ? 1 : 0;
     }
     return n;
 }
+
+// diagnostics (tests/test_layout.py): the layout plan of a model, with no sim
+// and no device — a window onto MgLayout (mg_layout.h)
+struct mg_layout {
+    MgLayout L;
+    std::vector<int32_t> scalars;
+};
+mg_layout* mg_debug_plan_layout(const mg_sim_params* p, const mg_model* m) {
+    if (!p || !m) { fail(MG_ERR_ARG, "null argument"); return nullptr; }
+    mg_layout* h = new mg_layout();
+    std::string err;
+    if (int rc_ = mg_plan_layout(*p, *m, layout_sizes(), h->L, err)) {
+        fail(rc_, "%s", err.c_str());
+        delete h;
+        return nullptr;
+    }
+    const MgLayout& L = h->L;
+    h->scalars = {L.nb, L.na, L.nd, L.nf, L.nf1, L.nf_rigid, L.n_coupled, L.n_pile, L.max_actor_dofs,
+                  L.roots_free ? 1 : 0, L.step_out_ok ? 1 : 0, (int32_t)L.groups.size(), (int32_t)L.env_groups.size()};
+    for (const MgArticGroup& g : L.groups)
+        h->scalars.insert(h->scalars.end(), {g.chain, g.aff, g.aff_b0, g.aff_d0, g.aff_ds, g.out_aff, g.out_g0, g.out_r0,
+                                             g.offset, g.count, g.step_offset, g.step_count, g.uni_mass ? 1 : 0, g.nl});
+    for (const MgEnvGroup& g : L.env_groups)
+        h->scalars.insert(h->scalars.end(), {g.tmpl, g.wide, g.max_free, g.offset, g.count});
+    return h;
+}
+int32_t mg_debug_layout_table(const mg_layout* h, int32_t which, const void** data, int64_t* count) {
+    if (!h || !data || !count) return fail(MG_ERR_ARG, "bad arguments");
+    const MgLayout& L = h->L;
+    auto give = [&](const auto& v) { *data = v.data(); *count = (int64_t)v.size(); return MG_OK; };
+    switch (which) {
+        case MG_LAYOUT_SCALARS: return give(h->scalars);
+        case MG_LAYOUT_PERM: return give(L.perm);
+        case MG_LAYOUT_ARTIC_SORTED: return give(L.artic_sorted);
+        case MG_LAYOUT_ARTIC_STEP: return give(L.artic_step);
+        case MG_LAYOUT_ENV_FLAT: return give(L.env_flat);
+        case MG_LAYOUT_PAIRS: return give(L.pairs);
+        case MG_LAYOUT_PILE_ROWS: return give(L.pile_rows);
+        case MG_LAYOUT_PILE_BODY: return give(L.pile_body);
+        case MG_LAYOUT_PILE_SLOTS: return give(L.pile_slots);
+        case MG_LAYOUT_PILE_PAIRS: return give(L.pile_pairs);
+        case MG_LAYOUT_CENV_ROW: return give(L.cenv_row);
+        case MG_LAYOUT_CENV_CTAB_OFF: return give(L.cenv_ctab_off);
+        default: return fail(MG_ERR_ARG, "no layout table %d", which);
+    }
+}
+void mg_debug_free_layout(mg_layout* h) { delete h; }
 
 // the S3 cube-pick controller (csrc/mg_ctrl.hip): independent of any sim, on
 // the caller's stream (torch's current stream: ordered with the refreshes that
@@ -2339,10 +1647,10 @@ int32_t mg_cube_pick_step(const mg_cube_pick_args* a, void* stream) {
     return MG_OK;
 }
 
-int32_t mg_num_free_bodies(mg_sim* s) { return s ? s->nf : 0; }
-int32_t mg_num_articulations(mg_sim* s) { return s ? s->nartic : 0; }
-int32_t mg_num_coupled_envs(mg_sim* s) { return s ? s->n_coupled : 0; }
-int32_t mg_num_pile_envs(mg_sim* s) { return s ? s->n_pile : 0; }
+int32_t mg_num_free_bodies(mg_sim* s) { return s ? s->layout.nf : 0; }
+int32_t mg_num_articulations(mg_sim* s) { return s ? s->layout.nartic : 0; }
+int32_t mg_num_coupled_envs(mg_sim* s) { return s ? s->layout.n_coupled : 0; }
+int32_t mg_num_pile_envs(mg_sim* s) { return s ? s->layout.n_pile : 0; }
 
 int32_t mg_refresh_actor_root_state(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
@@ -2355,15 +1663,15 @@ int32_t mg_refresh_actor_root_state(mg_sim* s, float* dst, int32_t dst_host, voi
         s->out_cap == cid)
         return MG_OK;   // written by the step kernel (MG_FUSE_STEP_OUT)
     if (!dst_host && dst && dst == s->bind_root && s->bind_rb && (s->fusion & MG_FUSE_REFRESH) &&
-        fuse_here(s, cid) && s->na > 0) {
+        fuse_here(s, cid) && s->layout.na > 0) {
         // the bound root and rigid-body tensors in one launch
-        HIP_TRY(mg_launch_gather_rb_root(s->d_state, s->nb, MG_STATE_N, s->d_perm, s->nb, s->bind_rb, s->d_body_actor,
+        HIP_TRY(mg_launch_gather_rb_root(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, s->bind_rb, s->d_body_actor,
                                          dst, st));
         s->rb_gen = s->state_gen;
         s->rb_cap = cid;
         return MG_OK;
     }
-    return refresh_rows(s, s->d_state, s->nb, MG_STATE_N, s->d_actor_root, s->na, dst, dst_host, st);
+    return refresh_rows(s, s->d_state, s->layout.nb, MG_STATE_N, s->d_actor_root, s->layout.na, dst, dst_host, st);
 }
 int32_t mg_refresh_rigid_body_state(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
@@ -2375,7 +1683,7 @@ int32_t mg_refresh_rigid_body_state(mg_sim* s, float* dst, int32_t dst_host, voi
     if (bound && (s->fusion & (MG_FUSE_REFRESH | MG_FUSE_STEP_OUT)) && s->rb_gen == s->state_gen &&
         s->rb_cap == capture_id(st))
         return MG_OK;   // served by the paired gather / the step kernel of the same capture (or eagerly)
-    const int rc = refresh_rows(s, s->d_state, s->nb, MG_STATE_N, s->d_perm, s->nb, dst, dst_host, st);
+    const int rc = refresh_rows(s, s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, dst, dst_host, st);
     if (rc == MG_OK && bound) {
         s->rb_gen = s->state_gen;
         s->rb_cap = capture_id(st);
@@ -2387,31 +1695,31 @@ int32_t mg_refresh_dof_state(mg_sim* s, float* dst, int32_t dst_host, void* stre
     if (!dst_host && dst && dst == s->bind_dof && (s->fusion & MG_FUSE_STEP_OUT) && s->dof_gen == s->dof_sgen &&
         s->dof_cap == capture_id((hipStream_t)stream))
         return MG_OK;   // written by the step kernel (MG_FUSE_STEP_OUT)
-    return refresh_rows(s, s->d_dof, s->nd, 2, nullptr, s->nd, dst, dst_host, (hipStream_t)stream);
+    return refresh_rows(s, s->d_dof, s->layout.nd, 2, nullptr, s->layout.nd, dst, dst_host, (hipStream_t)stream);
 }
 
 // ---- DOF force tensor --------------------------------------
 int32_t mg_enable_dof_forces(mg_sim* s, const int32_t* actor_on, int32_t n_actors) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (actor_on && n_actors != s->na)
-        return fail(MG_ERR_ARG, "DOF force flags for %d actors, the model has %d", n_actors, s->na);
+    if (actor_on && n_actors != s->layout.na)
+        return fail(MG_ERR_ARG, "DOF force flags for %d actors, the model has %d", n_actors, s->layout.na);
     // the flags decide which kernels a simulate launches: a graph captured
     // before the call would replay the old launches
     if (s->capturing)
         return fail(MG_ERR_STATE, "DOF force reporting changed after the step was captured into a graph (the replays "
                     "keep the old launches); call it before the capture, or after an eager simulate");
     HIP_TRY(hipSetDevice(s->device));
-    std::vector<float> on((size_t)std::max(s->nd, 1), 0.0f);
+    std::vector<float> on((size_t)std::max(s->layout.nd, 1), 0.0f);
     int n = 0;
     if (actor_on)
-        for (int a = 0; a < s->na; ++a)
+        for (int a = 0; a < s->layout.na; ++a)
             if (actor_on[a])
-                for (int d = s->h_actor_dof[a]; d < s->h_actor_dof[a + 1]; ++d) { on[d] = 1.0f; ++n; }
+                for (int d = s->layout.actor_dof[a]; d < s->layout.actor_dof[a + 1]; ++d) { on[d] = 1.0f; ++n; }
     // rows of actors that stop reporting, or that no kernel steps, read 0
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(s->d_dof_frc, 0, (size_t)std::max(s->nd, 1) * sizeof(float)));
-    if (s->nd > 0)
-        HIP_TRY(hipMemcpy(s->d_dof_frc + s->nd, on.data(), (size_t)s->nd * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(s->d_dof_frc, 0, (size_t)std::max(s->layout.nd, 1) * sizeof(float)));
+    if (s->layout.nd > 0)
+        HIP_TRY(hipMemcpy(s->d_dof_frc + s->layout.nd, on.data(), (size_t)s->layout.nd * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
     s->dof_frc_n = n;
     return MG_OK;
@@ -2419,17 +1727,17 @@ int32_t mg_enable_dof_forces(mg_sim* s, const int32_t* actor_on, int32_t n_actor
 
 int32_t mg_refresh_dof_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (!dst && s->nd > 0) return fail(MG_ERR_ARG, "null destination");
+    if (!dst && s->layout.nd > 0) return fail(MG_ERR_ARG, "null destination");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->nd == 0) return MG_OK;
+    if (s->layout.nd == 0) return MG_OK;
     hipStream_t st = (hipStream_t)stream;
     if (!dst_host) {
-        HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->nd, s->nd, dst, st));
+        HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->layout.nd, s->layout.nd, dst, st));
         return MG_OK;
     }
-    if (int rc = ensure_stage(s, (size_t)s->nd, 0)) return rc;
-    HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->nd, s->nd, s->d_stage, st));
-    HIP_TRY(hipMemcpyAsync(dst, s->d_stage, (size_t)s->nd * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (int rc = ensure_stage(s, (size_t)s->layout.nd, 0)) return rc;
+    HIP_TRY(mg_launch_dof_force_rows(s->d_dof_frc, s->d_dof_frc + s->layout.nd, s->layout.nd, s->d_stage, st));
+    HIP_TRY(hipMemcpyAsync(dst, s->d_stage, (size_t)s->layout.nd * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MG_OK;
 }
@@ -2449,13 +1757,13 @@ int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) 
     std::string err;
     for (int i = 0; i < n; ++i) {
         const mg_force_sensor& f = host[i];
-        if (f.body < 0 || f.body >= s->nb) return fail(MG_ERR_ARG, "force sensor %d: body %d out of range", i, f.body);
+        if (f.body < 0 || f.body >= s->layout.nb) return fail(MG_ERR_ARG, "force sensor %d: body %d out of range", i, f.body);
         bool fin = true;
         float q2 = 0.0f;
         for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(f.p[k]);
         for (int k = 0; k < 4; ++k) { fin = fin && std::isfinite(f.q[k]); q2 += f.q[k] * f.q[k]; }
         if (!fin || !(q2 > 0.0f)) return fail(MG_ERR_ARG, "force sensor %d: the local pose must be finite, its rotation not zero", i);
-        if (s->h_body_artic[f.body] < 0 && err.empty()) {
+        if (s->layout.body_artic[f.body] < 0 && err.empty()) {
             char buf[256];
             snprintf(buf, sizeof buf, "force sensor %d on rigid body %d: a single-body actor has no joint to measure "
                      "(and the free-body and pile kernels keep no contact moment); force sensors sit on bodies of "
@@ -2468,21 +1776,21 @@ int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) 
     // neighbouring instances
     struct Lane { int tmpl, slot, art, row; };
     std::vector<Lane> lanes;
-    std::vector<int> art_slot(s->h_artic_info.size(), 0), art_id(s->h_artic_info.size(), -1);
+    std::vector<int> art_slot(s->layout.artic_info.size(), 0), art_id(s->layout.artic_info.size(), -1);
     std::vector<int> sart, hist0;
-    std::vector<char> tmpl_env(s->h_atmpl.size() / MG_ATMPL_I_N, 0);
+    std::vector<char> tmpl_env(s->layout.atmpl.size() / MG_ATMPL_I_N, 0);
     int nhb = 0, nsave = 0;
     if (err.empty())
         for (int i = 0; i < n; ++i) {
-            const int a = s->h_body_artic[host[i].body];
-            const mg_sim::ArticInfo& ai = s->h_artic_info[a];
+            const int a = s->layout.body_artic[host[i].body];
+            const MgArticInfo& ai = s->layout.artic_info[a];
             if (art_id[a] < 0) {
                 art_id[a] = (int)hist0.size();
-                const int ndof = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 2];
-                const int nl = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 1], l0 = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 0];
+                const int ndof = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 2];
+                const int nl = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 1], l0 = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 0];
                 int nbody = 0;
-                for (int l = 0; l < nl; ++l) nbody += s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] >= 0 ? 1 : 0;
-                const int row[MG_SART_I_N] = {s->h_perm[ai.g0], ai.d0, ndof, nsave};
+                for (int l = 0; l < nl; ++l) nbody += s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] >= 0 ? 1 : 0;
+                const int row[MG_SART_I_N] = {s->layout.perm[ai.g0], ai.d0, ndof, nsave};
                 sart.insert(sart.end(), row, row + MG_SART_I_N);
                 hist0.push_back(nhb);
                 nhb += nbody;
@@ -2500,17 +1808,17 @@ int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) 
     for (int t = 0; t < nl_; ++t) {
         const Lane& L = lanes[t];
         const mg_force_sensor& f = host[L.row];
-        const mg_sim::ArticInfo& ai = s->h_artic_info[s->h_body_artic[f.body]];
-        const int l0 = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 0], nl = s->h_atmpl[ai.tmpl * MG_ATMPL_I_N + 1];
+        const MgArticInfo& ai = s->layout.artic_info[s->layout.body_artic[f.body]];
+        const int l0 = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 0], nl = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 1];
         // the sensor body's link, and its subtree (links in topological order:
         // a link joins when its parent is in)
         int ls = -1;
         for (int l = 0; l < nl; ++l)
-            if (s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] == f.body - ai.g0) ls = l;
+            if (s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] == f.body - ai.g0) ls = l;
         if (ls < 0) return fail(MG_ERR_ARG, "force sensor %d: body %d is no link of its articulation", L.row, f.body);
         unsigned mask = 1u << ls;
         for (int l = ls + 1; l < nl; ++l) {
-            const int p = s->h_link_i[(size_t)(l0 + l) * MG_LINK_I_N + 0];
+            const int p = s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 0];
             if (p >= 0 && ((mask >> p) & 1u)) mask |= 1u << l;
         }
         si[(size_t)MG_SENS_I_G0 * nl_ + t] = ai.g0;
@@ -2528,44 +1836,21 @@ int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) 
     }
     // fresh device buffers, committed at the end: an error leaves the table as it was
     HIP_TRY(hipDeviceSynchronize());
-    int *d_i = nullptr, *d_sart = nullptr, *d_flag = nullptr;
-    float *d_f = nullptr, *d_hist = nullptr, *d_save = nullptr, *d_out = nullptr;
-    auto drop = [&]() {
-        void* ps[] = {d_i, d_sart, d_flag, d_f, d_hist, d_save, d_out};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-    };
+    SensBufs B;
     if (nl_ > 0) {
-        hipError_t e = dalloc(&d_i, si.size());
-        if (e == hipSuccess) e = dalloc(&d_f, sf.size());
-        if (e == hipSuccess) e = dalloc(&d_sart, sart.size());
-        if (e == hipSuccess) e = dalloc(&d_flag, (size_t)2 * nart + 1);
-        if (e == hipSuccess) e = dalloc(&d_hist, (size_t)12 * nhb);
-        if (e == hipSuccess) e = dalloc(&d_save, (size_t)nsave);
-        if (e == hipSuccess) e = dalloc(&d_out, (size_t)6 * nl_);
-        if (e == hipSuccess && !s->d_ctorque) {
-            e = dalloc(&s->d_ctorque, (size_t)3 * std::max(s->nb, 1));
-            if (e == hipSuccess) e = hipMemset(s->d_ctorque, 0, (size_t)3 * std::max(s->nb, 1) * sizeof(float));
-        }
-        if (e == hipSuccess) e = hipMemcpy(d_i, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_f, sf.data(), sf.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_sart, sart.data(), sart.size() * sizeof(int), hipMemcpyHostToDevice);
+        hipError_t e = B.d_sens_i.upload(si);
+        if (e == hipSuccess) e = B.d_sens_f.upload(sf);
+        if (e == hipSuccess) e = B.d_sart_i.upload(sart);
         // no frame held yet: every articulation's first frame reads 0
-        if (e == hipSuccess) e = hipMemset(d_flag, 0, ((size_t)2 * nart + 1) * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(d_hist, 0, (size_t)12 * std::max(nhb, 1) * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(d_save, 0, (size_t)std::max(nsave, 1) * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(d_out, 0, (size_t)6 * nl_ * sizeof(float));
+        if (e == hipSuccess) e = B.d_sens_flag.zero((size_t)2 * nart + 1);
+        if (e == hipSuccess) e = B.d_sens_hist.zero((size_t)12 * nhb);
+        if (e == hipSuccess) e = B.d_sens_save.zero((size_t)nsave);
+        if (e == hipSuccess) e = B.d_sens_out.zero((size_t)6 * nl_);
+        if (e == hipSuccess && !s->d_ctorque) e = s->d_ctorque.zero((size_t)3 * std::max(s->layout.nb, 1));
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            drop();
-            return fail(MG_ERR_DEVICE, "force sensor table: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(MG_ERR_DEVICE, "force sensor table: %s", hipGetErrorString(e));
     }
-    void* old[] = {s->d_sens_i, s->d_sens_f, s->d_sart_i, s->d_sens_flag, s->d_sens_hist, s->d_sens_save, s->d_sens_out};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
-    s->d_sens_i = d_i; s->d_sens_f = d_f; s->d_sart_i = d_sart; s->d_sens_flag = d_flag;
-    s->d_sens_hist = d_hist; s->d_sens_save = d_save; s->d_sens_out = d_out;
+    static_cast<SensBufs&>(*s) = std::move(B);
     s->sensors.assign(host, host + n);
     s->n_sens = nl_;
     s->n_sart = nart;
@@ -2601,55 +1886,48 @@ int32_t mg_set_contact_reporting(mg_sim* s, int32_t on, int32_t capacity) {
                     "keep the old launches); call it before the capture, or after an eager simulate");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
-    void* old[] = {s->d_crep_cenv, s->d_crep_cenv_n, s->d_crep_col, s->d_crep_free, s->d_crep_free_n, s->d_crep_pile, s->d_crep_pile_n, s->d_crep_env, s->d_crep_blk, s->d_crep_out, s->d_crep_hdr};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
-    s->d_crep_free = nullptr; s->d_crep_free_n = nullptr; s->d_crep_env = nullptr; s->d_crep_blk = nullptr;
-    s->d_crep_pile = nullptr; s->d_crep_pile_n = nullptr;
-    s->d_crep_cenv = nullptr; s->d_crep_cenv_n = nullptr; s->d_crep_col = nullptr;
-    s->d_crep_out = nullptr; s->d_crep_hdr = nullptr;
+    static_cast<CrepBufs&>(*s) = CrepBufs();
     s->crep_on = false;
     s->crep_valid = false;
     s->crep_capacity = 0;
     if (!on) return MG_OK;
-    const int nfree = s->nf_rigid, ncenv = s->n_coupled, npile = s->n_pile, nown = nfree + ncenv + npile;
+    const MgLayout& L = s->layout;
+    const int nfree = L.nf_rigid, ncenv = L.n_coupled, npile = L.n_pile, nown = nfree + ncenv + npile;
     const int cenv_cap = 2 * MG_ENV_MAXCT_WIDE;
     const long long worst = (long long)nfree * MG_CREP_FREE_CAP + (long long)ncenv * cenv_cap +
                             (long long)npile * MG_PILE_MAXPT;
     if (worst > (1ll << 30)) return fail(MG_ERR_UNSUPPORTED, "contact reporting: %lld staged entries", worst);
     const int cap = capacity > 0 ? capacity : (int)std::max(worst, 1ll);
-    HIP_TRY(dalloc(&s->d_crep_free, (size_t)std::max(nfree, 1) * MG_CREP_FREE_CAP * MG_CREP_N));
-    HIP_TRY(dalloc(&s->d_crep_free_n, (size_t)std::max(nfree, 1)));
-    HIP_TRY(dalloc(&s->d_crep_cenv, (size_t)std::max(ncenv, 1) * cenv_cap * MG_CREP_N));
-    HIP_TRY(dalloc(&s->d_crep_cenv_n, (size_t)std::max(ncenv, 1)));
-    HIP_TRY(dalloc(&s->d_crep_col, (size_t)std::max(ncenv, 1)));
-    HIP_TRY(hipMemset(s->d_crep_cenv_n, 0, (size_t)std::max(ncenv, 1) * sizeof(int)));
-    if (ncenv > 0)
-        HIP_TRY(hipMemcpy(s->d_crep_col, s->h_cenv_row.data(), (size_t)ncenv * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(dalloc(&s->d_crep_pile, (size_t)std::max(npile, 1) * MG_PILE_MAXPT * MG_CREP_N));
-    HIP_TRY(dalloc(&s->d_crep_pile_n, (size_t)std::max(npile, 1)));
-    HIP_TRY(dalloc(&s->d_crep_env, (size_t)std::max(nown, 1)));
-    HIP_TRY(dalloc(&s->d_crep_blk, (size_t)(nown + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK + 1));
-    HIP_TRY(dalloc(&s->d_crep_out, (size_t)cap));
-    HIP_TRY(dalloc(&s->d_crep_hdr, 2));
+    // fresh buffers, committed at the end: a failure leaves reporting off and nothing half set
+    CrepBufs B;
+    HIP_TRY(B.d_crep_free.alloc((size_t)std::max(nfree, 1) * MG_CREP_FREE_CAP * MG_CREP_N));
+    HIP_TRY(B.d_crep_free_n.zero((size_t)nfree));
+    HIP_TRY(B.d_crep_cenv.alloc((size_t)std::max(ncenv, 1) * cenv_cap * MG_CREP_N));
+    HIP_TRY(B.d_crep_cenv_n.zero((size_t)ncenv));
+    HIP_TRY(B.d_crep_col.upload(L.cenv_row.data(), (size_t)ncenv));
+    HIP_TRY(B.d_crep_pile.alloc((size_t)std::max(npile, 1) * MG_PILE_MAXPT * MG_CREP_N));
+    HIP_TRY(B.d_crep_pile_n.zero((size_t)npile));
+    // owner -> env: free bodies are their own actors' roots (owner = storage
+    // slot), then the coupled envs and the pile envs, each by env index
+    std::vector<int> env(L.slot_env.begin(), L.slot_env.begin() + nfree);
+    env.insert(env.end(), L.cenv_env.begin(), L.cenv_env.end());
+    env.insert(env.end(), L.pile_env.begin(), L.pile_env.end());
+    HIP_TRY(B.d_crep_env.upload(env));
+    HIP_TRY(B.d_crep_blk.alloc((size_t)(nown + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK + 1));
+    HIP_TRY(B.d_crep_out.alloc((size_t)cap));
+    HIP_TRY(B.d_crep_hdr.zero(2));
     if (!s->h_crep_hdr) {
-        HIP_TRY(hipHostMalloc((void**)&s->h_crep_hdr, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer((void**)&s->d_crep_hdr_alias, s->h_crep_hdr, 0));
+        HostBuf<int> h;
+        int* d = nullptr;
+        HIP_TRY(h.alloc(2, true));
+        HIP_TRY(hipHostGetDevicePointer((void**)&d, h, 0));
+        s->h_crep_hdr = std::move(h);
+        s->d_crep_hdr_alias = d;
     }
     s->h_crep_hdr[0] = 0;
     s->h_crep_hdr[1] = 0;
-    HIP_TRY(hipMemset(s->d_crep_free_n, 0, (size_t)std::max(nfree, 1) * sizeof(int)));
-    HIP_TRY(hipMemset(s->d_crep_pile_n, 0, (size_t)std::max(npile, 1) * sizeof(int)));
-    HIP_TRY(hipMemset(s->d_crep_hdr, 0, 2 * sizeof(int)));
-    // owner -> env: free bodies are their own actors' roots (owner = storage
-    // slot), then the coupled envs and the pile envs, each by env index
-    if (nown > 0) {
-        std::vector<int> env(s->h_slot_env.begin(), s->h_slot_env.begin() + nfree);
-        env.insert(env.end(), s->h_cenv_env.begin(), s->h_cenv_env.end());
-        env.insert(env.end(), s->h_pile_env.begin(), s->h_pile_env.end());
-        HIP_TRY(hipMemcpy(s->d_crep_env, env.data(), (size_t)nown * sizeof(int), hipMemcpyHostToDevice));
-    }
     HIP_TRY(hipDeviceSynchronize());
+    static_cast<CrepBufs&>(*s) = std::move(B);
     s->crep_capacity = cap;
     s->crep_on = true;
     return MG_OK;
@@ -2683,7 +1961,7 @@ int32_t mg_refresh_rigid_contacts(mg_sim* s, mg_rigid_contact* dst, int32_t cap,
 
 int32_t mg_refresh_net_contact_force(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    return refresh_rows(s, s->d_cforce, s->nb, 3, s->d_perm, s->nb, dst, dst_host, (hipStream_t)stream);
+    return refresh_rows(s, s->d_cforce, s->layout.nb, 3, s->d_perm, s->layout.nb, dst, dst_host, (hipStream_t)stream);
 }
 
 int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, const int32_t* idx,
@@ -2698,7 +1976,7 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
     s->state_gen++;
     const unsigned long long cid = capture_id(st);
     s->last_set_deferred = 0;
-    if (!src_host && !idx && s->roots_free && (s->fusion & MG_FUSE_ROOT_SET) && fuse_here(s, cid)) {
+    if (!src_host && !idx && s->layout.roots_free && (s->fusion & MG_FUSE_ROOT_SET) && fuse_here(s, cid)) {
         if (s->pend_root && s->pend_root_cap != cid)
             if (int rc_ = flush_root(s, st)) return rc_;
         s->pend_root = src;   // read by the next simulate (a later full set replaces it)
@@ -2706,15 +1984,17 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
         s->last_set_deferred = 1;
         return MG_OK;
     }
-    if (src_host && !idx && s->roots_free && cid == 0) {
+    if (src_host && !idx && s->layout.roots_free && cid == 0) {
         // CPU pipeline, full set: copied at the call into the library's own buffer
         // (Isaac Gym's copy-at-set), read by the next simulate's step kernel like
         // a fused device set — or by the scatter a reader of the state issues first
-        const size_t bytes = (size_t)s->na * MG_STATE_N * sizeof(float);
+        const size_t bytes = (size_t)s->layout.na * MG_STATE_N * sizeof(float);
         s->pend_root = nullptr;     // a later full set replaces an earlier deferred one
         if (!s->h_root_in) {        // page-locked and device-mapped: the step kernel reads it over PCIe
-            HIP_TRY(hipHostMalloc((void**)&s->h_root_in, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_TRY(hipHostGetDevicePointer((void**)&s->d_root_in_alias, s->h_root_in, 0));
+            HostBuf<float> h;
+            HIP_TRY(h.alloc(bytes / sizeof(float), true));
+            HIP_TRY(hipHostGetDevicePointer((void**)&s->d_root_in_alias, h, 0));
+            s->h_root_in = std::move(h);
             HIP_TRY(hipEventCreateWithFlags(&s->root_ev, hipEventDisableTiming));
         }
         if (s->root_ev_pending) HIP_TRY(hipEventSynchronize(s->root_ev));   // its last reader is done
@@ -2725,10 +2005,10 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
         return MG_OK;
     }
     if (int rc_ = flush_root(s, st)) return rc_;
-    int rc = stage_src(s, src, src_host, (size_t)s->na * MG_STATE_N, idx, n_idx, st, &dsrc, &didx);
+    int rc = stage_src(s, src, src_host, (size_t)s->layout.na * MG_STATE_N, idx, n_idx, st, &dsrc, &didx);
     if (rc) return rc;
-    HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_actor_root, didx, idx ? n_idx : s->na, s->na,
-                                   s->d_state, s->nb, st));
+    HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_actor_root, didx, idx ? n_idx : s->layout.na, s->layout.na,
+                                   s->d_state, s->layout.nb, st));
     return MG_OK;
 }
 
@@ -2741,11 +2021,11 @@ int32_t mg_set_rigid_body_state(mg_sim* s, const float* src, int32_t src_host, v
     const int* didx;
     if (int rc_ = flush_root(s, st)) return rc_;
     s->state_gen++;
-    int rc = stage_src(s, src, src_host, (size_t)s->nb * MG_STATE_N, nullptr, 0, st, &dsrc, &didx);
+    int rc = stage_src(s, src, src_host, (size_t)s->layout.nb * MG_STATE_N, nullptr, 0, st, &dsrc, &didx);
     if (rc) return rc;
     // free bodies only: rows are selected through the free-body list
-    HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_perm, s->d_free_global, s->nf, s->nb, s->d_state,
-                                   s->nb, st));
+    HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_perm, s->d_free_global, s->layout.nf, s->layout.nb, s->d_state,
+                                   s->layout.nb, st));
     return MG_OK;
 }
 
@@ -2754,14 +2034,14 @@ int32_t mg_set_dof_state(mg_sim* s, const float* src, int32_t src_host, const in
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     s->dof_sgen++;
     s->last_set_deferred = 0;
-    return set_dof_columns(s, src, src_host, 2, s->d_dof, s->d_dof + s->nd, idx, n_idx, (hipStream_t)stream);
+    return set_dof_columns(s, src, src_host, 2, s->d_dof, s->d_dof + s->layout.nd, idx, n_idx, (hipStream_t)stream);
 }
 // column k of the DOF targets; a device-resident full set is read by the next
 // simulate's articulation kernels (MG_FUSE_DOF_TARGETS), else a scatter / copy
 static int32_t set_dof_target(mg_sim* s, int k, const float* src, int32_t src_host, const int32_t* idx,
                               int32_t n_idx, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (s->nd == 0) return MG_OK;
+    if (s->layout.nd == 0) return MG_OK;
     if (!src) return fail(MG_ERR_ARG, "null source tensor");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->device));
@@ -2776,7 +2056,7 @@ static int32_t set_dof_target(mg_sim* s, int k, const float* src, int32_t src_ho
         return MG_OK;
     }
     if (int rc_ = flush_tgt(s, k, st)) return rc_;
-    return set_dof_columns(s, src, src_host, 1, s->d_dof_tgt + (size_t)k * s->nd, nullptr, idx, n_idx, st);
+    return set_dof_columns(s, src, src_host, 1, s->d_dof_tgt + (size_t)k * s->layout.nd, nullptr, idx, n_idx, st);
 }
 int32_t mg_set_dof_position_target(mg_sim* s, const float* src, int32_t src_host, const int32_t* idx,
                                    int32_t n_idx, void* stream) {
@@ -2793,7 +2073,7 @@ int32_t mg_set_dof_actuation_force(mg_sim* s, const float* src, int32_t src_host
 
 int32_t mg_set_dof_props(mg_sim* s, const float* props_host) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (s->nd == 0) return MG_OK;
+    if (s->layout.nd == 0) return MG_OK;
     if (!props_host) return fail(MG_ERR_ARG, "null props");
     HIP_TRY(hipSetDevice(s->device));
     // joint friction: the table decides which kernels a simulate launches (a
@@ -2804,7 +2084,7 @@ int32_t mg_set_dof_props(mg_sim* s, const float* props_host) {
     if (pl.changed && s->capturing)
         return fail(MG_ERR_STATE, "DOF friction changed which kernels step the DOFs after the step was captured into a "
                     "graph (the replays keep the old launches); set it before the capture, or after an eager simulate");
-    std::vector<float> dp = to_soa(props_host, s->nd, MG_DOFPROP_N);
+    std::vector<float> dp = to_soa(props_host, s->layout.nd, MG_DOFPROP_N);
     if (pl.changed) HIP_TRY(hipDeviceSynchronize());   // the old launches read the old table to their end
     HIP_TRY(hipMemcpy(s->d_dof_props, dp.data(), dp.size() * sizeof(float), hipMemcpyHostToDevice));
     if (int rc_ = jfr_commit(s, pl)) return rc_;
@@ -2825,10 +2105,10 @@ int32_t mg_apply_rigid_body_force(mg_sim* s, const float* force, const float* to
         if (!parts[k]) continue;
         const float* dsrc;
         const int* didx;
-        int rc = stage_src(s, parts[k], src_host, (size_t)s->nb * 3, nullptr, 0, st, &dsrc, &didx);
+        int rc = stage_src(s, parts[k], src_host, (size_t)s->layout.nb * 3, nullptr, 0, st, &dsrc, &didx);
         if (rc) return rc;
-        HIP_TRY(mg_launch_scatter_rows(dsrc, 3, s->d_perm, nullptr, s->nb, s->nb, s->d_ext + (size_t)k * 3 * s->nb,
-                                       s->nb, st));
+        HIP_TRY(mg_launch_scatter_rows(dsrc, 3, s->d_perm, nullptr, s->layout.nb, s->layout.nb, s->d_ext + (size_t)k * 3 * s->layout.nb,
+                                       s->layout.nb, st));
         if (src_host) HIP_TRY(hipStreamSynchronize(st));  // staging buffer is reused by the next part
     }
     s->ext_pending = true;
@@ -2857,13 +2137,13 @@ static int refresh_jac_mm(mg_sim* s, int32_t tmpl, float* jdst, float* mdst, int
         mout = mdst ? s->d_stage + jtot : nullptr;
     }
     MgArticArgs A{};
-    A.na = g->count; A.nb = s->nb; A.nd = s->nd;
+    A.na = g->count; A.nb = s->layout.nb; A.nd = s->layout.nd;
     A.artic_i = s->d_artic + (size_t)g->offset * MG_ARTIC_I_N;
     A.tmpl = g->tmpl; A.nl = g->nl; A.ndof = g->ndof; A.fixed_base = g->fixed_base; A.nbl = g->nbody;
     A.link_f = s->d_link_f + (size_t)g->first_link * MG_LINK_F_N;
     A.link_i = s->d_link_i + (size_t)g->first_link * MG_LINK_I_N;
     A.state = s->d_state; A.mass = s->d_mass;
-    A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->nd;
+    A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
     if (mtot > 0) HIP_TRY(hipMemsetAsync(mout, 0, mtot * sizeof(float), st));
     HIP_TRY(mg_launch_jacobian(A, jout, mout, st));
     if (dst_host) {
@@ -2894,19 +2174,19 @@ int32_t mg_set_render_bodies(mg_sim* s, const int32_t* env_body_first, const flo
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (!env_body_first || !color || !seg) return fail(MG_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(s->device));
-    const int ne = s->nenv;
-    if (env_body_first[0] != 0 || env_body_first[ne] != s->nb) return fail(MG_ERR_ARG, "env_body_first must span [0, num_bodies]");
+    const int ne = s->layout.nenv;
+    if (env_body_first[0] != 0 || env_body_first[ne] != s->layout.nb) return fail(MG_ERR_ARG, "env_body_first must span [0, num_bodies]");
     std::vector<MgRShape> rs;
     std::vector<int> first(ne + 1, 0);
     for (int e = 0; e < ne; ++e) {
         first[e] = (int)rs.size();
         if (env_body_first[e + 1] < env_body_first[e]) return fail(MG_ERR_ARG, "env_body_first not monotone");
         for (int b = env_body_first[e]; b < env_body_first[e + 1]; ++b) {
-            const int t = s->h_body_tmpl[b];
-            const int sh0 = s->h_tbi[(size_t)t * MG_TBODY_I_N + 0], nsh = s->h_tbi[(size_t)t * MG_TBODY_I_N + 1];
+            const int t = s->layout.body_tmpl[b];
+            const int sh0 = s->layout.tbi[(size_t)t * MG_TBODY_I_N + 0], nsh = s->layout.tbi[(size_t)t * MG_TBODY_I_N + 1];
             for (int k = 0; k < nsh; ++k) {
                 MgRShape r{};
-                r.slot = s->h_perm[b];
+                r.slot = s->layout.perm[b];
                 r.shape = sh0 + k;
                 r.seg = seg[b];
                 r.r = color[3 * (size_t)b + 0]; r.g = color[3 * (size_t)b + 1]; r.b = color[3 * (size_t)b + 2];
@@ -2918,13 +2198,10 @@ int32_t mg_set_render_bodies(mg_sim* s, const int32_t* env_body_first, const flo
                         (int)rs.size() - first[e], MG_RENDER_MAX_SHAPES);
     }
     first[ne] = (int)rs.size();
-    if (s->d_rshapes) (void)hipFree(s->d_rshapes);
-    if (s->d_env_shape_first) (void)hipFree(s->d_env_shape_first);
-    s->d_rshapes = nullptr; s->d_env_shape_first = nullptr;
-    HIP_TRY(dalloc(&s->d_rshapes, rs.size()));
-    HIP_TRY(dalloc(&s->d_env_shape_first, (size_t)ne + 1));
-    if (!rs.empty()) HIP_TRY(hipMemcpy(s->d_rshapes, rs.data(), rs.size() * sizeof(MgRShape), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_env_shape_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+    s->d_rshapes.reset();
+    s->d_env_shape_first.reset();
+    HIP_TRY(s->d_rshapes.upload(rs));
+    HIP_TRY(s->d_env_shape_first.upload(first));
     s->n_rshapes = (int)rs.size();
     s->render_ready = true;
     return MG_OK;
@@ -2933,9 +2210,9 @@ int32_t mg_set_render_bodies(mg_sim* s, const int32_t* env_body_first, const flo
 int32_t mg_snapshot_render_state(mg_sim* s, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     HIP_TRY(hipSetDevice(s->device));
-    if (!s->d_rstate) HIP_TRY(dalloc(&s->d_rstate, (size_t)s->nb * MG_STATE_N));
+    if (!s->d_rstate) HIP_TRY(s->d_rstate.alloc((size_t)s->layout.nb * MG_STATE_N));
     if (int rc_ = flush_root(s, (hipStream_t)stream)) return rc_;
-    HIP_TRY(hipMemcpyAsync(s->d_rstate, s->d_state, (size_t)s->nb * MG_STATE_N * sizeof(float),
+    HIP_TRY(hipMemcpyAsync(s->d_rstate, s->d_state, (size_t)s->layout.nb * MG_STATE_N * sizeof(float),
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     s->rstate_valid = true;
     return MG_OK;
@@ -2960,14 +2237,14 @@ int32_t mg_render_cameras(mg_sim* s, const mg_camera* cams, int32_t n, void* str
         long long blocks = 0;
         for (int i = 0; i < n; ++i) {
             const mg_camera& c = cams[i];
-            if (c.env < 0 || c.env >= s->nenv) return fail(MG_ERR_ARG, "camera %d: env %d out of range", i, c.env);
+            if (c.env < 0 || c.env >= s->layout.nenv) return fail(MG_ERR_ARG, "camera %d: env %d out of range", i, c.env);
             if (c.width <= 0 || c.height <= 0 || (long long)c.width * c.height > (1ll << 30))
                 return fail(MG_ERR_ARG, "camera %d: bad size %dx%d", i, c.width, c.height);
-            if (c.body >= s->nb) return fail(MG_ERR_ARG, "camera %d: body %d out of range", i, c.body);
+            if (c.body >= s->layout.nb) return fail(MG_ERR_ARG, "camera %d: body %d out of range", i, c.body);
             if (!(c.fx > 0.0f) || !(c.fy > 0.0f)) return fail(MG_ERR_ARG, "camera %d: bad focal length", i);
             MgRenderCam& d = dev[i];
             d.env = c.env; d.w = c.width; d.h = c.height;
-            d.slot = c.body >= 0 ? s->h_perm[c.body] : -1;
+            d.slot = c.body >= 0 ? s->layout.perm[c.body] : -1;
             d.follow = c.follow;
             d.blk0 = (int)blocks;
             const long long npx = (long long)c.width * c.height;
@@ -2984,9 +2261,8 @@ int32_t mg_render_cameras(mg_sim* s, const mg_camera* cams, int32_t n, void* str
         }
         if (blocks > (1ll << 31) - 1) return fail(MG_ERR_ARG, "too many pixels in one render call");
         if (n > s->cam_cap) {
-            if (s->d_cams) (void)hipFree(s->d_cams);
-            s->d_cams = nullptr;
-            HIP_TRY(dalloc(&s->d_cams, (size_t)n));
+            s->cam_cap = 0;
+            HIP_TRY(s->d_cams.alloc((size_t)n));
             s->cam_cap = n;
         }
         HIP_TRY(hipMemcpy(s->d_cams, dev.data(), (size_t)n * sizeof(MgRenderCam), hipMemcpyHostToDevice));
@@ -2995,7 +2271,7 @@ int32_t mg_render_cameras(mg_sim* s, const mg_camera* cams, int32_t n, void* str
         s->cam_blocks = (int)blocks;
     }
     MgRenderArgs A{};
-    A.ncam = n; A.nb = s->nb; A.cams = s->d_cams; A.state = s->d_rstate; A.shapes = s->d_shapes;
+    A.ncam = n; A.nb = s->layout.nb; A.cams = s->d_cams; A.state = s->d_rstate; A.shapes = s->d_shapes;
     A.hulls = s->d_hulls;
     A.uniform_nblk = s->cam_dev[0].nblk;
     for (int i = 1; i < n; ++i)
