@@ -634,6 +634,10 @@ typedef struct mg_layout mg_layout;
 #define MG_LAYOUT_PILE_PAIRS    9
 #define MG_LAYOUT_CENV_ROW      10  /* coupled env k (env order) -> its row of ENV_FLAT */
 #define MG_LAYOUT_CENV_CTAB_OFF 11  /* ... -> float offset of its contact-table record */
+/* facts about the single-shape free bodies that pick the free-body kernel's
+ * build; [0]: each one's shape is a box at the body origin with the body's
+ * orientation, or absent (the box-only build, mg_last_rigid_form) */
+#define MG_LAYOUT_FREE_FLAGS    12
 #define MG_LAYOUT_HEAD_N        13
 #define MG_LAYOUT_GROUP_N       14
 #define MG_LAYOUT_ENVGROUP_N    5
@@ -646,6 +650,18 @@ int         mg_env_carry_floats(void);
  * articulation kernel in one simulate. */
 int32_t     mg_num_free_bodies(mg_sim* sim);
 int32_t     mg_num_articulations(mg_sim* sim);
+/* Diagnostics: the kernel form of the last simulate's single-shape free-body
+ * launch (csrc/mg_rigid.hip k_rigid_step1), as MG_RIGID_FORM_* bits: WIDE (more
+ * waves than one resident round; else one-round), REC (a one-round launch
+ * that reads its per-slot indices from the packed slot record; else from the
+ * separate index arrays) and BOX (candidates compiled for the box alone).
+ * There is no third, "affine" way to the indices: a build that computed them
+ * from the kernel arguments was measured and left out.
+ * -1: the last simulate made no such launch, or none was made yet. */
+#define MG_RIGID_FORM_WIDE 1
+#define MG_RIGID_FORM_REC  2
+#define MG_RIGID_FORM_BOX  4
+int32_t     mg_last_rigid_form(mg_sim* sim);
 /* Number of envs stepped by the coupled per-env kernel (envs whose bodies can
  * touch each other under the actor_coll rule, e.g. the Franka cube-pick scene,
  * and every env holding a floating-base articulation). */

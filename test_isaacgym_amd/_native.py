@@ -31,8 +31,10 @@ MG_DEBUG_GROUP_N = 8       # include/migym.h mg_debug_artic_groups
 # mg_debug_layout_table (include/migym.h): table ids, scalar block strides
 (MG_LAYOUT_SCALARS, MG_LAYOUT_PERM, MG_LAYOUT_ARTIC_SORTED, MG_LAYOUT_ARTIC_STEP, MG_LAYOUT_ENV_FLAT,
  MG_LAYOUT_PAIRS, MG_LAYOUT_PILE_ROWS, MG_LAYOUT_PILE_BODY, MG_LAYOUT_PILE_SLOTS, MG_LAYOUT_PILE_PAIRS,
- MG_LAYOUT_CENV_ROW, MG_LAYOUT_CENV_CTAB_OFF) = range(12)
+ MG_LAYOUT_CENV_ROW, MG_LAYOUT_CENV_CTAB_OFF, MG_LAYOUT_FREE_FLAGS) = range(13)
 MG_LAYOUT_HEAD_N, MG_LAYOUT_GROUP_N, MG_LAYOUT_ENVGROUP_N = 13, 14, 5
+# mg_last_rigid_form (include/migym.h): bits of the last single-shape free-body launch
+MG_RIGID_FORM_WIDE, MG_RIGID_FORM_REC, MG_RIGID_FORM_BOX = 1, 2, 4
 MG_ATMPL_I_N = 4
 MG_ACOLL_N = 4
 
@@ -189,6 +191,7 @@ def _load():
         "mg_last_step_ms": (ctypes.c_float, [vp]),
         "mg_step_time_stats": (i32, [vp, i32, vp, vp, vp]),
         "mg_num_free_bodies": (i32, [vp]),
+        "mg_last_rigid_form": (i32, [vp]),
         "mg_num_articulations": (i32, [vp]),
         "mg_num_coupled_envs": (i32, [vp]),
         "mg_num_pile_envs": (i32, [vp]),
@@ -252,6 +255,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
     "mg_joint_friction_stats",
     "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
+    "mg_last_rigid_form",
 )
 
 
@@ -269,15 +273,16 @@ def check(rc, what):
         raise MigymError("%s failed (%d): %s" % (what, rc, last_error()))
 
 
-def plan_layout(params, model):
+def plan_layout(params, model, tables=range(12)):
     """The layout plan of a model (mg_debug_plan_layout; no GPU): {table id: numpy array}, or
-    MigymError with the library's refusal."""
+    MigymError with the library's refusal. `tables`: the ids to return (the first twelve by
+    default; MG_LAYOUT_FREE_FLAGS on request)."""
     h = lib.mg_debug_plan_layout(ctypes.byref(params), ctypes.byref(model))
     if not h:
         raise MigymError(last_error())
     try:
         out = {}
-        for which in range(12):
+        for which in tables:
             data, n = ctypes.c_void_p(), ctypes.c_int64()
             check(lib.mg_debug_layout_table(h, which, ctypes.byref(data), ctypes.byref(n)), "mg_debug_layout_table")
             dt = {MG_LAYOUT_PILE_PAIRS: np.uint32, MG_LAYOUT_CENV_CTAB_OFF: np.int64}.get(which, np.int32)

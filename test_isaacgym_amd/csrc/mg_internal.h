@@ -99,6 +99,11 @@ struct MgRigidArgs {
     int*         crep_n;      // [nf]
     const int*   crep_body;   // [nb]
     int          crep_stride;
+    // every single-shape free body's shape is a box at the body origin with the
+    // body's orientation, or absent (MgLayout::free_flags): a one-round launch
+    // with the slot record then runs the build whose candidate search is
+    // compiled for that box alone (the BOX build of k_rigid_step1)
+    int          box_only;
 };
 
 // Rigid contact list (mg_contact.hip). A reporting build of a
@@ -466,7 +471,8 @@ hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t
 extern "C" int mg_env_carry_floats(void);   // per-env record sizes of the coupled step (mg_env.hip)
 extern "C" int mg_env_ctab_floats(void);
 int mg_env_ctab_record_floats(int wide);   // one env's contact table in a 16- / 64-lane group
-hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s);
+// form (optional): the MG_RIGID_FORM_* bits of the single-shape launch, -1 when there was none
+hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s, int* form = nullptr);
 hipError_t mg_launch_artic_step(const MgStep& P, const MgArticArgs& A, hipStream_t s);
 hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s);
 hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStream_t s);

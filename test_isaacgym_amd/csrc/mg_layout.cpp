@@ -772,6 +772,22 @@ void plan_slot_tables(const mg_model* m, MgLayout& L) {
     L.tbi.assign(m->tmpl_body_i, m->tmpl_body_i + (size_t)L.ntb * MG_TBODY_I_N);
 }
 
+// Facts about the single-shape free bodies that pick the free-body kernel's
+// build (MgLayout::free_flags). [0], box_only: every such body's shape is a box
+// at the body origin with the body's orientation, or absent.
+void plan_free_flags(const MgLayoutSizes& z, MgLayout& L) {
+    // shape records as plan_trec copied them: type at [0] (< 0: none), the
+    // shape's position at [4..6], its rotation (x, y, z, w) at [7..10]
+    bool box_only = true;
+    for (int i = 0; i < L.nf1 && box_only; ++i) {
+        const float* sh = &L.trec[(size_t)L.slot_rec[i][1] * z.trec_n + MG_TBODY_F_N];
+        if (sh[0] < 0.0f) continue;
+        box_only = (int)sh[0] == MG_SHAPE_BOX && sh[4] == 0.0f && sh[5] == 0.0f && sh[6] == 0.0f && sh[7] == 0.0f &&
+                   sh[8] == 0.0f && sh[9] == 0.0f && sh[10] == 1.0f;
+    }
+    L.free_flags.assign(1, box_only ? 1 : 0);
+}
+
 }  // namespace
 
 int mg_plan_layout(const mg_sim_params& p, const mg_model& model, const MgLayoutSizes& z, MgLayout& L, std::string& err) {
@@ -787,5 +803,6 @@ int mg_plan_layout(const mg_sim_params& p, const mg_model& model, const MgLayout
     plan_env_groups(m, z, L, w);
     plan_trec(m, z, L);
     plan_slot_tables(m, L);
+    plan_free_flags(z, L);
     return MG_OK;
 }

@@ -70,6 +70,11 @@ struct MgLayout {
     std::vector<int> root_row;     // [nb] the same while roots_free holds its way, else partly -1
     std::vector<int> body_actor;   // [nb] global body -> actor it is the root of, or -1
     std::vector<std::array<int, 4>> slot_rec;   // [max(nb, 1)] {root_row, tmpl_int, order, slot_actor} (MgSlotRec)
+    // free_flags[0] (box_only): every single-shape free body (slots 0..nf1-1)
+    // has a box at the body origin with the body's orientation as its shape, or
+    // no shape. A shape's type and pose are fixed at upload: no call rewrites
+    // the shape or template records afterwards.
+    std::vector<int> free_flags;
     std::vector<float> state0, mass0;           // SoA [13][nb], [12][nb] in storage order
     std::vector<float> trec;                    // [ntb][trec_n] compact template records (k_rigid_step1)
     std::vector<float> shape_obb;               // [max(ns, 1)][obb_n] shape-frame boxes

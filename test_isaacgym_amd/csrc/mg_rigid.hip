@@ -240,18 +240,22 @@ __device__ __forceinline__ V3 origin_from_com(V3 xc, Q4 q, V3 com) {
 
 // Candidates of one shape: emit(k, point, separation, mu, e) with k the static
 // candidate index within the shape (box corner bits zyx, capsule end 0/1, the
-// k-th deepest hull vertex).
-template <class B, class F>
+// k-th deepest hull vertex). BOX: the caller's shapes are all boxes at the body
+// origin with the body's orientation (MgRigidArgs::box_only): only that branch
+// is compiled, the same operations on a box as in the general build.
+template <bool BOX = false, class B, class F>
 __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, const float* sh, Q4 q, V3 x,
                                                  const float* hulls, F&& emit) {
-    const int type = (int)sh[0];
+    const int type = BOX ? MG_SHAPE_BOX : (int)sh[0];
     // shape pose in the world: a shape at the body origin with the body's
     // orientation (the usual URDF box / sphere) skips the composition
     Q4 qs = q;
     V3 cs = x;
-    if (!shape_pose_identity(sh)) {
-        qs = qmul(q, q4(sh[7], sh[8], sh[9], sh[10]));
-        cs = vadd(x, qrot(q, v3(sh[4], sh[5], sh[6])));
+    if constexpr (!BOX) {
+        if (!shape_pose_identity(sh)) {
+            qs = qmul(q, q4(sh[7], sh[8], sh[9], sh[10]));
+            cs = vadd(x, qrot(q, v3(sh[4], sh[5], sh[6])));
+        }
     }
     const float mu = 0.5f * (sh[11] + P.mu_ground);
     const float e = 0.5f * (sh[12] + P.e_ground);
@@ -769,8 +773,8 @@ __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an
 // CREP (the reporting builds): cr is the body's staging record
 // (null: a dead lane), crs its stride, gbody the body's global index; the last
 // substep's points and anchors are stored there with the impulses that enter
-// fsum. Returns the number of entries staged.
-template <bool PACK, bool ATTR, bool CREP, class B>
+// fsum. Returns the number of entries staged. BOX: shape_candidates' box build.
+template <bool PACK, bool ATTR, bool CREP, bool BOX = false, class B>
 __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const float* T, V3& x, Q4& q, V3& v,
                                            V3& w, V3& fsum, float invm, V3 invI, Q4 iq, V3 com, bool has_ext,
                                            V3 fext, V3 text, const float* hulls, float* gp, int gstride,
@@ -879,7 +883,7 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
         const float clear = G.dn(x) + P.pd;
         const bool far = rho >= 0.0f && clear - rho > P.contact_offset + 1e-3f * (1.0f + fabsf(clear) + rho);
         if (__any(has_shape && !far) && has_shape)
-            shape_candidates(G, P, sh, q, x, hulls, [&](int k, V3 p, float sep, float, float) {
+            shape_candidates<BOX>(G, P, sh, q, x, hulls, [&](int k, V3 p, float sep, float, float) {
                 // selects, not a branch: the candidates of a wave's bodies pass
                 // the test on different lanes
                 const bool c = sep < P.contact_offset;
@@ -1078,9 +1082,12 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
 #ifndef MG_RIGID1_WIDE_WAVES
 #define MG_RIGID1_WIDE_WAVES 3
 #endif
-template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false, bool CREP = false>
+// BOX (one-round launches with the slot record whose shapes are all plain
+// boxes, MgRigidArgs::box_only): the candidates are compiled for the box alone.
+template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false, bool CREP = false, bool BOX = false>
 __global__ void __launch_bounds__(64, UPZ && WIDE && !CREP ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
 k_rigid_step1(MgStep P, MgRigidArgs A) {
+    static_assert(!BOX || (!WIDE && REC), "BOX: a one-round build that reads the slot record");
     extern __shared__ float s_trec[];
     const int i = (WIDE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 64 + threadIdx.x;
     RSTAMP(0);
@@ -1251,15 +1258,17 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
         }
     }
     if constexpr (UPZ) {
-        crk = rigid_body1<!WIDE, ATTR, CREP>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr,
-                                             fext, text, A.hulls, gp, A.gstride, pr, at, cr, A.crep_stride, gbody);
+        crk = rigid_body1<!WIDE, ATTR, CREP, BOX>(BasisZ{}, P, T, x, q, v, w, fsum, invm, invI, iq, com,
+                                                  A.ext != nullptr, fext, text, A.hulls, gp, A.gstride, pr, at, cr,
+                                                  A.crep_stride, gbody);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        crk = rigid_body1<!WIDE, ATTR, CREP>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr, fext,
-                                             text, A.hulls, gp, A.gstride, pr, at, cr, A.crep_stride, gbody);
+        crk = rigid_body1<!WIDE, ATTR, CREP, BOX>(G, P, T, x, q, v, w, fsum, invm, invI, iq, com, A.ext != nullptr,
+                                                  fext, text, A.hulls, gp, A.gstride, pr, at, cr, A.crep_stride,
+                                                  gbody);
     }
     if constexpr (CREP) {
         if (live) A.crep_n[b] = crk;
@@ -1371,7 +1380,8 @@ static int mg_cu_count() {
 
 // A.free_ids lists the single-shape bodies first (A.nf1 of them), then the
 // multi-shape ones; each group is its own launch.
-hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s) {
+hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s, int* form) {
+    if (form) *form = -1;
     if (A.nf <= 0) return hipSuccess;
     const bool upz = mg_step_is_upz(P);
     MgRigidArgs A1 = A, A2 = A;
@@ -1409,6 +1419,7 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
             // step in which form (and so every value) is then the same with
             // reporting on and off
             const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
+            if (form) *form = wide ? MG_RIGID_FORM_WIDE : 0;
 #define MG_K1C(U, W, T) MG_LAUNCH((k_rigid_step1<U, false, W, T, false, true>), dim3(blocks), dim3(64), 0, s, P, A1)
 #define MG_K1C_T(U, W) do { if (at) MG_K1C(U, W, true); else MG_K1C(U, W, false); } while (0)
             if (upz && wide) MG_K1C_T(true, true);
@@ -1434,13 +1445,19 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         // wide: more waves than one resident round (4 SIMDs x 3 or 2 waves per
         // CU). Such a launch is issue-bound, not latency-bound: it dispatches
         // longest-first (back to front: the free-body order, migym_capi.cpp) and
-        // solves with the scalar rows (tgs_z's packed pairs save latency, not
-        // issue slots: DESIGN.md §3.2).
+        // solves with the scalar rows (tgs_z's packed pairs are fewer
+        // instructions for a wave alone on its SIMD, but each holds the issue
+        // slots of two scalar ones when waves share it: DESIGN.md §3.2).
         const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
         const size_t lds = (size_t)A.ntb * MG_TREC_N * sizeof(float);
         // a one-round launch with the packed slot record: the builds that read it
         // (REC; the others keep the four index arrays in their argument registers)
         const bool rec = A1.slot_rec != nullptr;
+        // the box-only build (candidates compiled for the box alone): a one-round
+        // launch with the slot record over a z-up ground, its template records
+        // staged in LDS, no attractor, every shape a plain box
+        const bool box = upz && !wide && rec && !A1.attr_idx && lds <= MG_TREC_LDS_MAX && A.box_only;
+        if (form) *form = wide ? MG_RIGID_FORM_WIDE : (rec ? MG_RIGID_FORM_REC : 0) | (box ? MG_RIGID_FORM_BOX : 0);
 #define MG_K1(U, L) \
     do { \
         if (wide) MG_LAUNCH((k_rigid_step1<U, L, true, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
@@ -1456,6 +1473,8 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
             else if (wide) MG_LAUNCH((k_rigid_step1<false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
             else if (rec) MG_LAUNCH((k_rigid_step1<false, false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
             else MG_LAUNCH((k_rigid_step1<false, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
+        } else if (box) {
+            MG_LAUNCH((k_rigid_step1<true, true, false, false, true, false, true>), dim3(blocks), dim3(64), lds, s, P, A1);
         } else if (lds <= MG_TREC_LDS_MAX) {
             if (upz) MG_K1(true, true);
             else MG_K1(false, true);

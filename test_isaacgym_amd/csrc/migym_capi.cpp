@@ -377,6 +377,7 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     hipStream_t last_stream = nullptr;
     bool stepped = false;
     bool capturing = false;       // the last simulate was recorded into a graph
+    int rigid_form = -1;          // MG_RIGID_FORM_* bits of the last free-body launch (mg_last_rigid_form)
     // ring of per-simulate event pairs for live kernel timing (bench.py roofline)
     static constexpr int kRing = 256;
     static constexpr int kKern = 8;   // kernels timed per simulate (dispatch timestamps)
@@ -905,6 +906,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     const MgStep P = make_step(s->params);
+    s->rigid_form = -1;   // this simulate's, or none (mg_last_rigid_form)
     {   // deferred sets of another capture (or of the eager stream while capturing):
         // applied here as ordinary launches, not read by this step's kernels
         const unsigned long long cid = capture_id(st);
@@ -1120,6 +1122,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
         A.trec = s->d_trec; A.ntb = s->layout.ntb;
         A.slot_rec = s->d_slot_rec;
+        A.box_only = s->layout.free_flags.empty() ? 0 : s->layout.free_flags[0];
         A.gpatch = s->d_gpatch;
         A.gstride = std::max(s->layout.nf1, 1);
         A.ext = s->ext_pending ? s->d_ext : nullptr;
@@ -1147,7 +1150,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
             A.out_body = s->d_slot_global;     // internal slot -> global body
             A.out_root_row = s->d_slot_actor;
         }
-        HIP_TRY(mg_launch_rigid_step(P, A, st));
+        HIP_TRY(mg_launch_rigid_step(P, A, st, &s->rigid_form));
         if (reads_root_in) {
             HIP_TRY(hipEventRecord(s->root_ev, st));
             s->root_ev_pending = true;
@@ -1628,6 +1631,7 @@ int32_t mg_debug_layout_table(const mg_layout* h, int32_t which, const void** da
         case MG_LAYOUT_PILE_PAIRS: return give(L.pile_pairs);
         case MG_LAYOUT_CENV_ROW: return give(L.cenv_row);
         case MG_LAYOUT_CENV_CTAB_OFF: return give(L.cenv_ctab_off);
+        case MG_LAYOUT_FREE_FLAGS: return give(L.free_flags);
         default: return fail(MG_ERR_ARG, "no layout table %d", which);
     }
 }
@@ -1647,6 +1651,7 @@ int32_t mg_cube_pick_step(const mg_cube_pick_args* a, void* stream) {
     return MG_OK;
 }
 
+int32_t mg_last_rigid_form(mg_sim* s) { return s ? s->rigid_form : -1; }
 int32_t mg_num_free_bodies(mg_sim* s) { return s ? s->layout.nf : 0; }
 int32_t mg_num_articulations(mg_sim* s) { return s ? s->layout.nartic : 0; }
 int32_t mg_num_coupled_envs(mg_sim* s) { return s ? s->layout.n_coupled : 0; }
