@@ -34,12 +34,21 @@
 //   - the row updates fuse the impulse accumulation (fmaf) and clamp the
 //     friction impulse with one v_med3_f32;
 //   - the +Z ground (make_step's basis n = z, t1 = y, t2 = -x) is a template
-//     specialisation with the cross / dot products written out.
+//     specialisation with the cross / dot products written out;
+//   - a wave of a one-round launch is alone on its SIMD and bound by
+//     instruction issue, where a packed f32 instruction does two lanes' worth
+//     of work in one slot: beside the +Z solver (tgs_zp), the patch update,
+//     the row constants with the anchor rows, and Iw are formed on f2 pairs
+//     (mg_pair.h; MG_RIGID1_PACK_GEOM, builds without attractor or report),
+//     and qmat(q) is formed once per substep for Iw and the candidates. Each
+//     half is the scalar form's operation, so results are unchanged; the wide
+//     forms and k_rigid_step keep the scalar code.
 // Multi-shape bodies run k_rigid_step (8 shift-register slots, a second launch).
 // The C restatement is oracle/migym_oracle.c:rigid_body_step (same slot order,
 // same specialisation, same evaluation order).
 #include "mg_internal.h"
 #include "mg_math.h"
+#include "mg_pair.h"
 #include "mg_attractor.h"
 #include "mg_contact.h"
 
@@ -133,22 +142,13 @@ struct BasisZ {
     __device__ __forceinline__ V3 fn(V3 v, float dl, float invm) const { return v3(v.x, v.y, fmaf(dl, invm, v.z)); }
     __device__ __forceinline__ V3 f1(V3 v, float dl, float invm) const { return v3(v.x, fmaf(dl, invm, v.y), v.z); }
     __device__ __forceinline__ V3 f2(V3 v, float dl, float invm) const { return v3(fmaf(-dl, invm, v.x), v.y, v.z); }
-    // symmul / vdot with the zero component of r x d dropped (symmul's term order)
-    __device__ __forceinline__ V3 iwn(const S3& I, V3 r) const {
-        const float a = r.y, b = -r.x;   // r x n = (a, b, 0)
-        return v3(I.xx * a + I.xy * b, I.xy * a + I.yy * b, I.xz * a + I.yz * b);
-    }
-    __device__ __forceinline__ V3 iw1(const S3& I, V3 r) const {
-        const float a = -r.z, c = r.x;   // r x t1 = (a, 0, c)
-        return v3(I.xx * a + I.xz * c, I.xy * a + I.yz * c, I.xz * a + I.zz * c);
-    }
-    __device__ __forceinline__ V3 iw2(const S3& I, V3 r) const {
-        const float b = -r.z, c = r.y;   // r x t2 = (0, b, c)
-        return v3(I.xy * b + I.xz * c, I.yy * b + I.yz * c, I.yz * b + I.zz * c);
-    }
-    __device__ __forceinline__ float kn(V3 r, V3 In) const { return r.y * In.x + -r.x * In.y; }
-    __device__ __forceinline__ float k1(V3 r, V3 I1) const { return -r.z * I1.x + r.x * I1.z; }
-    __device__ __forceinline__ float k2(V3 r, V3 I2) const { return -r.z * I2.y + r.y * I2.z; }
+    // symmul / vdot with the zero component of r x d dropped (mg_pair.h)
+    __device__ __forceinline__ V3 iwn(const S3& I, V3 r) const { return z_iwn(I, r); }
+    __device__ __forceinline__ V3 iw1(const S3& I, V3 r) const { return z_iw1(I, r); }
+    __device__ __forceinline__ V3 iw2(const S3& I, V3 r) const { return z_iw2(I, r); }
+    __device__ __forceinline__ float kn(V3 r, V3 In) const { return z_kn(r, In); }
+    __device__ __forceinline__ float k1(V3 r, V3 I1) const { return z_k1(r, I1); }
+    __device__ __forceinline__ float k2(V3 r, V3 I2) const { return z_k2(r, I2); }
 };
 
 // clamp x to [-lim, lim] (lim >= 0): the median of three, one instruction
@@ -243,9 +243,12 @@ __device__ __forceinline__ V3 origin_from_com(V3 xc, Q4 q, V3 com) {
 // k-th deepest hull vertex). BOX: the caller's shapes are all boxes at the body
 // origin with the body's orientation (MgRigidArgs::box_only): only that branch
 // is compiled, the same operations on a box as in the general build.
-template <bool BOX = false, class B, class F>
+// PK (the one-round builds with their geometry on packed pairs, mg_pair.h): Rq
+// is qmat(q), formed once per substep by the caller; a box with the body's
+// orientation takes it as its own matrix.
+template <bool BOX = false, bool PK = false, class B, class F>
 __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, const float* sh, Q4 q, V3 x,
-                                                 const float* hulls, F&& emit) {
+                                                 const float* hulls, F&& emit, const M3* Rq = nullptr) {
     const int type = BOX ? MG_SHAPE_BOX : (int)sh[0];
     // shape pose in the world: a shape at the body origin with the body's
     // orientation (the usual URDF box / sphere) skips the composition
@@ -263,7 +266,15 @@ __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, co
         // the face whose outward normal is most opposed to n: axis i* maximises
         // |n . axis_i| (first index on ties), side s* = -sign(n . axis_i*); its 4
         // corners are the candidates k = 0..3 (signs of the two other axes)
-        const M3 Rs = qmat(qs);
+        M3 Rs;
+        if constexpr (PK) {
+            Rs = *Rq;
+            if constexpr (!BOX) {
+                if (!shape_pose_identity(sh)) Rs = qmat(qs);
+            }
+        } else {
+            Rs = qmat(qs);
+        }
         const float d0 = G.dn(Rs.c0), d1 = G.dn(Rs.c1), d2 = G.dn(Rs.c2);
         const float ad0 = fabsf(d0), ad1 = fabsf(d1), ad2 = fabsf(d2);
         int ia = 0;
@@ -531,6 +542,12 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
 #ifndef MG_RIGID1_SHAPE_REGS
 #define MG_RIGID1_SHAPE_REGS 1
 #endif
+// One-round launches without an attractor or a contact report form their
+// geometry on packed f32 pairs (mg_pair.h); 0 builds the scalar form for A/B
+// runs (tools/build_variant.sh).
+#ifndef MG_RIGID1_PACK_GEOM
+#define MG_RIGID1_PACK_GEOM 1
+#endif
 // Friction is PhysX's patch friction, as in the coupled
 // step (§3.6.1): the body-ground pair's contacts form one patch whose friction
 // acts at up to two anchors, each fixed on the body (body frame) and on the
@@ -623,6 +640,72 @@ __device__ __forceinline__ void ground_patch_update(const B& G, GPatch& R, V3 x,
     R = N;
 }
 
+// ground_patch_update on packed f32 pairs (mg_pair.h), for the one-round
+// launches (a lone wave is issue-bound: DESIGN.md §3.2). The same values by the
+// same operations, two at a time: the held anchors' world copies with their
+// distance tests, qrot(q, nA) beside qrot_inv(q, n0) as one rotation by the
+// quaternion pair (q, conj q), each scan candidate's e0 / e1 and dj0 / dj1 with
+// the scan points kept as the pair (w0, w1), and the two closing qrot_inv.
+// Compares and selects act on the halves.
+template <class B>
+__device__ __forceinline__ void ground_patch_update_pk(const B& G, GPatch& R, V3 x, Q4 q, V3 n0, const V3 (&p)[4],
+                                                       const float (&s0)[4], const bool (&on)[4], float fot,
+                                                       float corr) {
+    const float c2 = corr * corr;
+    const V3 z3 = v3(0.0f, 0.0f, 0.0f);
+    int cnt = R.cnt;
+    // (qrot(q, nA), qrot_inv(q, n0))
+    const V3x2 nn = qrotq2(q4x2(q, qconj(q)), v3x2(R.nA, n0));
+    const float nd = G.dn(v3lo(nn));
+    if (cnt > 0 && nd < MG_FP_NORMAL_COS) cnt = 0;
+    const V3x2 X = v3bc(x);
+    const V3x2 wa = vadd2(X, qrot2(q, v3x2(R.aA[0], R.aA[1])));
+    const V3x2 dv = vsub2(wa, v3x2(R.aB[0], R.aB[1]));
+    const f2 dq = vdot2(dv, dv);
+    const bool k0 = 0 < cnt && dq.x <= c2;
+    const bool k1 = 1 < cnt && dq.y <= c2;
+    const V3 wa0 = v3lo(wa), wa1 = v3hi(wa);
+    GPatch N;
+    N.aA[0] = vsel(k0, R.aA[0], vsel(k1, R.aA[1], z3));
+    N.aB[0] = vsel(k0, R.aB[0], vsel(k1, R.aB[1], z3));
+    N.aA[1] = vsel(k0 && k1, R.aA[1], z3);
+    N.aB[1] = vsel(k0 && k1, R.aB[1], z3);
+    V3x2 W = v3x2(vsel(k0, wa0, vsel(k1, wa1, z3)), z3);   // (w0, w1)
+    const int kept = (k0 ? 1 : 0) + (k1 ? 1 : 0);
+    int nc = kept;
+    float dd = 0.0f;
+    bool set0 = false, set1 = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool c = kept < 2 && on[j] && s0[j] <= fot;
+        const V3 pj = p[j];
+        const V3x2 E = vsub2(v3bc(pj), W);   // (e0, e1)
+        const f2 dj = vdot2(E, E);
+        const float dj0 = dj.x, dj1 = dj.y;
+        const bool a0 = c && nc == 0;
+        const bool a1 = c && nc == 1 && dj0 > c2;
+        const bool a2 = c && nc == 2 && dj0 > dj1 && dj0 > dd;
+        const bool a3 = c && nc == 2 && !(dj0 > dj1) && dj1 > dd;
+        const bool to0 = a0 || a3, to1 = a1 || a2;
+        dd = (a1 || a2) ? dj0 : (a3 ? dj1 : dd);
+        W.x = pk2(to0 ? pj.x : W.x.x, to1 ? pj.x : W.x.y);
+        W.y = pk2(to0 ? pj.y : W.y.x, to1 ? pj.y : W.y.y);
+        W.z = pk2(to0 ? pj.z : W.z.x, to1 ? pj.z : W.z.y);
+        set0 = set0 || to0;
+        set1 = set1 || to1;
+        nc = a0 ? 1 : (a1 ? 2 : nc);
+    }
+    const V3x2 bA = qrot_inv2(q, vsub2(W, X));
+    N.aA[0] = vsel(set0, v3lo(bA), N.aA[0]);
+    N.aB[0] = vsel(set0, v3lo(W), N.aB[0]);
+    N.aA[1] = vsel(set1, v3hi(bA), N.aA[1]);
+    N.aB[1] = vsel(set1, v3hi(W), N.aB[1]);
+    N.cnt = nc;
+    N.nA = vsel(kept > 0, R.nA, v3hi(nn));
+    N.dirty = R.dirty || !(kept == R.cnt && nc == kept);
+    R = N;
+}
+
 // Normal row of the branch-free solver: an inactive slot holds r = 0, s0 = 0
 // and kn = 0, so it computes ln = max(0 + 0 (tgt - vn), 0) = 0 and applies a
 // zero impulse. Anchor rows likewise (k = 0, r = 0: raw 0 within any bound).
@@ -657,10 +740,7 @@ __device__ __forceinline__ void row_normal1(const B& G, NRow& c, V3& v, V3& w, f
 // rounded fma / add / mul as the scalar form, so results are bit-identical to
 // the scalar loop and to the oracle; only the issue count drops. Used by
 // launches that fit in one resident round (the latency regime: DESIGN.md §3.2).
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk2(float a, float b) { return f2{a, b}; }
-__device__ __forceinline__ f2 bc2(float a) { return f2{a, a}; }
-__device__ __forceinline__ f2 pfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+// (f2, pk2, bc2, pfma: mg_pair.h)
 
 // lim1 = share * mu: an anchor row's bound per unit of the patch's normal impulse
 __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an)[2], float lim1, float e, V3& v,
@@ -781,6 +861,8 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
                                            const float (&pr)[MG_FP_N], const float* at, float* cr = nullptr,
                                            int crs = 0, int gbody = 0) {
     int crk = 0;
+    // geometry on packed pairs: the one-round builds without attractor or report
+    constexpr bool PKG = PACK && !ATTR && !CREP && MG_RIGID1_PACK_GEOM;
     const float lin_damp = T[0], ang_damp = T[1], max_lv = T[2], max_av = T[3], grav_on = T[4];
     // the shape record: wide launches read it from the template record (LDS
     // when staged) in each substep's candidate search — registers are scarcer
@@ -843,7 +925,20 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
     RSTAMP(2);   // patch record read
     q = qnormalize(q);
     for (int st = 0; st < P.substeps; ++st) {
-        const S3 Iw = sym_rdrt(qmat(inertia_frame(q, iq)), invI);
+        // PKG: qmat(q) is formed once per substep, for the candidates and, when
+        // the principal frame is the body's (inertia_frame's identity skip), for
+        // Iw: the same function of the same input; Iw's entries as pairs
+        M3 Rq;
+        S3P Ip;
+        S3 Iw;
+        if constexpr (PKG) {
+            Rq = qmat(q);
+            M3 Rp = Rq;
+            if (!(iq.x == 0.0f && iq.y == 0.0f && iq.z == 0.0f && iq.w == 1.0f)) Rp = qmat(qmul(q, iq));
+            Iw = sym_rdrt_p(Rp, invI, Ip);
+        } else {
+            Iw = sym_rdrt(qmat(inertia_frame(q, iq)), invI);
+        }
         const V3 xc = com_world(x, q, com);
 
         // 1. unconstrained velocity
@@ -883,7 +978,7 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
         const float clear = G.dn(x) + P.pd;
         const bool far = rho >= 0.0f && clear - rho > P.contact_offset + 1e-3f * (1.0f + fabsf(clear) + rho);
         if (__any(has_shape && !far) && has_shape)
-            shape_candidates<BOX>(G, P, sh, q, x, hulls, [&](int k, V3 p, float sep, float, float) {
+            shape_candidates<BOX, PKG>(G, P, sh, q, x, hulls, [&](int k, V3 p, float sep, float, float) {
                 // selects, not a branch: the candidates of a wave's bodies pass
                 // the test on different lanes
                 const bool c = sep < P.contact_offset;
@@ -891,7 +986,7 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
                 sl[k].r = vsel(c, vsub(p, xc), sl[k].r);
                 sl[k].s0 = c ? sep - P.rest_offset : sl[k].s0;
                 cp[k] = vsel(c, p, cp[k]);
-            });
+            }, &Rq);
         RUSE(sl[0].s0); RUSE(sl[3].r.z);
         if (st < 2) RSTAMP(4 + 6 * st);   // candidates
         bool any = false;
@@ -902,7 +997,10 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
             float cs0[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) cs0[j] = sl[j].s0;
-            ground_patch_update(G, R, x, q, n0, cp, cs0, on, P.fric_offset, P.fric_corr);
+            if constexpr (PKG)
+                ground_patch_update_pk(G, R, x, q, n0, cp, cs0, on, P.fric_offset, P.fric_corr);
+            else
+                ground_patch_update(G, R, x, q, n0, cp, cs0, on, P.fric_offset, P.fric_corr);
         } else {
             R.cnt = 0;
         }
@@ -912,38 +1010,78 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
         // 3. TGS (skipped by a wave in which no body touches the ground)
         V3 dx = v3(0.0f, 0.0f, 0.0f), dth = v3(0.0f, 0.0f, 0.0f);
         if (__any(any)) {
-            // contact constants (inactive slots: r = 0, so In = 0, kn = 0)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sl[j].In = G.iwn(Iw, sl[j].r);
-                sl[j].kn = on[j] ? 1.0f / (invm + G.kn(sl[j].r, sl[j].In)) : 0.0f;
-                sl[j].ln = 0.0f;
-                sl[j].vn0 = G.vn(v, w, sl[j].r);
-            }
-            // anchor rows at the anchors' body copies; the position sweeps close
-            // 80 % of the substep-start drift of their two copies
             ARow an[2];
             V3 awp[2];   // CREP: the anchors' body copies in the world
+            if constexpr (PKG && B::kPacked) {
+                // the same constants on packed pairs (mg_pair.h): the x, y of
+                // every Iw (r x d) as the pair the solver consumes, the slots'
+                // pre-solve normal velocities two at a time, the anchors' world
+                // copies, drifts and lever arms as one pair of vectors
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const bool act = a < R.cnt;
-                // formed on every lane, selected (a divergent branch cost more)
-                const V3 wa = vadd(x, qrot(q, R.aA[a]));
-                if constexpr (CREP) awp[a] = wa;
-                const V3 dr = vsub(wa, R.aB[a]);
-                const float kd = 0.8f * P.inv_h;
-                const V3 r = vsel(act, vsub(wa, xc), v3(0.0f, 0.0f, 0.0f));
-                const float e1 = act ? fminf(fmaxf(-G.d1(dr) * kd, -P.max_depen), P.max_depen) : 0.0f;
-                const float e2 = act ? fminf(fmaxf(-G.d2(dr) * kd, -P.max_depen), P.max_depen) : 0.0f;
-                an[a].r = r;
-                an[a].I1 = G.iw1(Iw, r);
-                an[a].I2 = G.iw2(Iw, r);
-                an[a].k1 = act ? 1.0f / (invm + G.k1(r, an[a].I1)) : 0.0f;
-                an[a].k2 = act ? 1.0f / (invm + G.k2(r, an[a].I2)) : 0.0f;
-                an[a].l1 = 0.0f;
-                an[a].l2 = 0.0f;
-                an[a].e1 = e1;
-                an[a].e2 = e2;
+                for (int j = 0; j < 4; ++j) {
+                    const f2 Ixy = z_iwn_xy(Ip, sl[j].r);
+                    sl[j].In = v3(Ixy.x, Ixy.y, z_iwn_z(Iw, sl[j].r));
+                    sl[j].kn = on[j] ? 1.0f / (invm + G.kn(sl[j].r, sl[j].In)) : 0.0f;
+                    sl[j].ln = 0.0f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j += 2) {
+                    const f2 vn0 = z_vn2(v, w, pk2(sl[j].r.y, sl[j + 1].r.y), pk2(-sl[j].r.x, -sl[j + 1].r.x));
+                    sl[j].vn0 = vn0.x;
+                    sl[j + 1].vn0 = vn0.y;
+                }
+                const V3x2 WA = vadd2(v3bc(x), qrot2(q, v3x2(R.aA[0], R.aA[1])));
+                const V3x2 DR = vsub2(WA, v3x2(R.aB[0], R.aB[1]));
+                const V3x2 RR = vsub2(WA, v3bc(xc));
+                const f2 kd2 = bc2(0.8f * P.inv_h);
+                const f2 E1 = -DR.y * kd2, E2 = -(-DR.x) * kd2;   // -d1(dr) kd, -d2(dr) kd
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    const bool act = a < R.cnt;
+                    const V3 r = vsel(act, a ? v3hi(RR) : v3lo(RR), v3(0.0f, 0.0f, 0.0f));
+                    const f2 I1xy = z_iw1_xy(Ip, r), I2xy = z_iw2_xy(Ip, r);
+                    an[a].r = r;
+                    an[a].I1 = v3(I1xy.x, I1xy.y, z_iw1_z(Iw, r));
+                    an[a].I2 = v3(I2xy.x, I2xy.y, z_iw2_z(Iw, r));
+                    an[a].k1 = act ? 1.0f / (invm + G.k1(r, an[a].I1)) : 0.0f;
+                    an[a].k2 = act ? 1.0f / (invm + G.k2(r, an[a].I2)) : 0.0f;
+                    an[a].l1 = 0.0f;
+                    an[a].l2 = 0.0f;
+                    an[a].e1 = act ? fminf(fmaxf(a ? E1.y : E1.x, -P.max_depen), P.max_depen) : 0.0f;
+                    an[a].e2 = act ? fminf(fmaxf(a ? E2.y : E2.x, -P.max_depen), P.max_depen) : 0.0f;
+                }
+            } else {
+                // contact constants (inactive slots: r = 0, so In = 0, kn = 0)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    sl[j].In = G.iwn(Iw, sl[j].r);
+                    sl[j].kn = on[j] ? 1.0f / (invm + G.kn(sl[j].r, sl[j].In)) : 0.0f;
+                    sl[j].ln = 0.0f;
+                    sl[j].vn0 = G.vn(v, w, sl[j].r);
+                }
+                // anchor rows at the anchors' body copies; the position sweeps close
+                // 80 % of the substep-start drift of their two copies
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    const bool act = a < R.cnt;
+                    // formed on every lane, selected (a divergent branch cost more)
+                    const V3 wa = vadd(x, qrot(q, R.aA[a]));
+                    if constexpr (CREP) awp[a] = wa;
+                    const V3 dr = vsub(wa, R.aB[a]);
+                    const float kd = 0.8f * P.inv_h;
+                    const V3 r = vsel(act, vsub(wa, xc), v3(0.0f, 0.0f, 0.0f));
+                    const float e1 = act ? fminf(fmaxf(-G.d1(dr) * kd, -P.max_depen), P.max_depen) : 0.0f;
+                    const float e2 = act ? fminf(fmaxf(-G.d2(dr) * kd, -P.max_depen), P.max_depen) : 0.0f;
+                    an[a].r = r;
+                    an[a].I1 = G.iw1(Iw, r);
+                    an[a].I2 = G.iw2(Iw, r);
+                    an[a].k1 = act ? 1.0f / (invm + G.k1(r, an[a].I1)) : 0.0f;
+                    an[a].k2 = act ? 1.0f / (invm + G.k2(r, an[a].I2)) : 0.0f;
+                    an[a].l1 = 0.0f;
+                    an[a].l2 = 0.0f;
+                    an[a].e1 = e1;
+                    an[a].e2 = e2;
+                }
             }
             // the anchors whose bound clamped a row in the last iteration, per
             // anchor and direction: the patch slips when every anchor it holds is
