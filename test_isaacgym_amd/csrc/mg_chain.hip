@@ -1012,8 +1012,10 @@ __device__ __forceinline__ void chain_body_q(const MgStep& P, const MgArticArgs&
 #endif
 }
 
-template <int NL, bool EXT, bool UNI, bool FRC>
+template <int NL, unsigned F>
 __global__ void __launch_bounds__(64, 2) k_artic_chain_q(MgStep P, MgArticArgs AA) {
+    static_assert(k_artic_chain_q_built(NL, F), "not a build of k_artic_chain_q (mg_forms.h)");
+    constexpr bool EXT = F & CF_EXT, UNI = F & CF_UNI, FRC = F & CF_FRC;
     if constexpr (UNI) {
         if (AA.uni[MG_CHAIN_UNI_DOFOK] != 0.0f) chain_body_q<NL, EXT, true, true, FRC>(P, AA);
         else chain_body_q<NL, EXT, true, false, FRC>(P, AA);
@@ -1027,8 +1029,10 @@ __global__ void __launch_bounds__(64, 2) k_artic_chain_q(MgStep P, MgArticArgs A
 // while every instance shared them keeps stepping correctly after a
 // set_actor_dof_properties makes one differ, as the per-lane
 // path reads d_dof_props in place.
-template <int NL, bool EXT, bool UNI, bool AFF, bool FRC>
+template <int NL, unsigned F>
 __global__ void __launch_bounds__(64, MG_CHAIN_WAVES) k_artic_chain(MgStep P, MgArticArgs AA) {
+    static_assert(k_artic_chain_built(NL, F), "not a build of k_artic_chain (mg_forms.h)");
+    constexpr bool EXT = F & CF_EXT, UNI = F & CF_UNI, AFF = F & CF_AFF, FRC = F & CF_FRC;
     __shared__ __align__(16) float s_rows[64 * NL * MG_STATE_N];
     __shared__ __align__(16) float s_root[64 * MG_STATE_N];
     if constexpr (UNI) {
@@ -1045,51 +1049,18 @@ __global__ void __launch_bounds__(64, MG_CHAIN_WAVES) k_artic_chain(MgStep P, Mg
 hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
     if (!A.chain || A.nl < 2 || A.nl > 4) return hipErrorNotSupported;
-    const int cb = (A.na + 63) / 64;
-#ifndef MG_CHAIN_QUAD_MAX
-#define MG_CHAIN_QUAD_MAX (64 * 1024)   // four lanes per chain up to this many lanes (one resident round)
-#endif
-    if ((long)A.na * 4 <= MG_CHAIN_QUAD_MAX) {
-        const int qb = (A.na * 4 + 63) / 64;
-#define MG_KQ2(NL, FRC)                                                                                  \
-    do {                                                                                                 \
-        if (A.ext) {                                                                                     \
-            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, true, true, FRC>), dim3(qb), dim3(64), 0, s, P, A);  \
-            else MG_LAUNCH((k_artic_chain_q<NL, true, false, FRC>), dim3(qb), dim3(64), 0, s, P, A);       \
-        } else {                                                                                         \
-            if (A.uni) MG_LAUNCH((k_artic_chain_q<NL, false, true, FRC>), dim3(qb), dim3(64), 0, s, P, A); \
-            else MG_LAUNCH((k_artic_chain_q<NL, false, false, FRC>), dim3(qb), dim3(64), 0, s, P, A);      \
-        }                                                                                                \
-    } while (0)
-    // the DOF-force builds only when the sim reports DOF forces (A.dof_frc)
-#define MG_KQ(NL) do { if (A.dof_frc) MG_KQ2(NL, true); else MG_KQ2(NL, false); } while (0)
-        if (A.nl == 2) MG_KQ(2);
-        else if (A.nl == 3) MG_KQ(3);
-        else MG_KQ(4);
-#undef MG_KQ2
-#undef MG_KQ
-        return hipGetLastError();
-    }
-#define MG_KC2(NL, FRC)                                                                                      \
-    do {                                                                                                     \
-        if (A.ext) {                                                                                         \
-            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, true, true, true, FRC>), dim3(cb), dim3(64), 0, s, P, A);   \
-            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, true, true, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);    \
-            else MG_LAUNCH((k_artic_chain<NL, true, false, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);              \
-        } else {                                                                                             \
-            if (A.uni && aff) MG_LAUNCH((k_artic_chain<NL, false, true, true, FRC>), dim3(cb), dim3(64), 0, s, P, A);  \
-            else if (A.uni) MG_LAUNCH((k_artic_chain<NL, false, true, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);   \
-            else MG_LAUNCH((k_artic_chain<NL, false, false, false, FRC>), dim3(cb), dim3(64), 0, s, P, A);             \
-        }                                                                                                    \
-    } while (0)
-#define MG_KC(NL) do { if (A.dof_frc) MG_KC2(NL, true); else MG_KC2(NL, false); } while (0)
     // the computed-row form when the upload found the rows affine (and the
-    // fused refresh's rows too, when it writes them)
+    // fused refresh's rows too, when it writes them); the DOF-force builds only
+    // when the sim reports DOF forces (A.dof_frc)
     const bool aff = MG_CHAIN_AFF && A.aff && ((A.out_rb == nullptr && A.out_root == nullptr) || A.out_aff);
-    if (A.nl == 2) MG_KC(2);
-    else if (A.nl == 3) MG_KC(3);
-    else MG_KC(4);
-#undef MG_KC
-#undef MG_KC2
-    return hipGetLastError();
+    const MgChainForm c = mg_chain_form(A.na, A.ext, A.uni, aff, A.dof_frc);
+    const bool ok = mg_with_int<2, 3, 4>(A.nl, [&](auto nl) {
+        constexpr int NL = decltype(nl)::value;
+        if (c.quad)   // four lanes per chain
+            return MG_LAUNCH_FORM(CF_BITS, c.f, k_artic_chain_q_built(NL, F), (k_artic_chain_q<NL, F>),
+                                  dim3((A.na * 4 + 63) / 64), 0, s, P, A);
+        return MG_LAUNCH_FORM(CF_BITS, c.f, k_artic_chain_built(NL, F), (k_artic_chain<NL, F>),
+                              dim3((A.na + 63) / 64), 0, s, P, A);
+    });
+    return ok ? hipGetLastError() : hipErrorNotSupported;
 }

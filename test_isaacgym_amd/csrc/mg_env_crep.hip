@@ -1,6 +1,7 @@
-// mg_env_crep.hip — the reporting builds of the coupled per-env step
-// (k_env_step<..., CREP>, the rigid contact list): mg_env.hip
-// compiled once more for these instantiations alone, beside the others, as
-// mg_env_sens.hip does for the contact-moment builds.
-#define MG_ENV_CREP_TU 1
-#include "mg_env.hip"
+// mg_env_crep.hip — k_env_step's reporting builds (MG_ENV_OBJ_CREP, mg_forms.h), with or without a
+// contact torque row (the rigid contact list).
+#include "mg_env_kernels.h"
+
+hipError_t mg_launch_env_step_crep(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    return env_step_launch<MG_ENV_OBJ_CREP>(maxl, form, s, P, A);
+}

@@ -1,6 +1,11 @@
-// mg_env_jfr.hip — the joint-friction builds of the coupled per-env step and
-// of the uncoupled lanes step (k_env_step<..., JFR>, k_artic_lanes<..., JFR>,
-// DESIGN.md §3.15): mg_env.hip compiled once more for these instantiations
-// alone, beside the others, as mg_env_sens.hip and mg_env_crep.hip do.
-#define MG_ENV_JFR_TU 1
-#include "mg_env.hip"
+// mg_env_jfr.hip — the joint-friction builds (MG_ENV_OBJ_JFR, mg_forms.h): k_env_step for a
+// coupled group whose envs hold a friction DOF, k_artic_lanes for the uncoupled instances that do. Friction
+// together with attractors, force sensors or contact reporting is refused by mg_simulate.
+#include "mg_env_kernels.h"
+
+hipError_t mg_launch_env_step_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    return env_step_launch<MG_ENV_OBJ_JFR>(maxl, form, s, P, A);
+}
+hipError_t mg_launch_artic_lanes_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgArticArgs& A) {
+    return artic_lanes_launch<MG_ENV_OBJ_JFR>(maxl, form, s, P, A);
+}

@@ -1,6 +1,7 @@
-// mg_env_sens.hip — the contact-moment builds of the coupled per-env step
-// (k_env_step<..., SENS>): mg_env.hip compiled a second time
-// for these instantiations alone, so that they build beside the others instead
-// of lengthening the one translation unit the build already waits for.
-#define MG_ENV_SENS_TU 1
-#include "mg_env.hip"
+// mg_env_sens.hip — k_env_step's contact-moment builds (MG_ENV_OBJ_SENS, mg_forms.h; force sensors,
+// DESIGN.md §3.13). An object of their own so that the library builds in parallel.
+#include "mg_env_kernels.h"
+
+hipError_t mg_launch_env_step_sens(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    return env_step_launch<MG_ENV_OBJ_SENS>(maxl, form, s, P, A);
+}

@@ -9,6 +9,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include "../../include/migym.h"
+#include "mg_forms.h"
 
 #define MG_MAX_CONTACTS 8     // contact slots per free body per substep
 #define MG_MAX_LINKS    32    // articulation links (more than 16: the 64-lane kernels)
@@ -42,9 +43,7 @@ struct MgStep {
 // bounding radius), then that shared mass row (MG_MASS_N floats)
 #define MG_TREC_N        (MG_TBODY_F_N + MG_SHAPE_STRIDE + MG_MASS_N)
 #define MG_TREC_MASS     (MG_TBODY_F_N + MG_SHAPE_STRIDE)
-#ifndef MG_TREC_LDS_MAX
-#define MG_TREC_LDS_MAX  (48 * 1024)
-#endif
+// staged up to MG_TREC_LDS_MAX bytes (mg_forms.h)
 
 // Every static per-slot index of the single-shape free-body step in one 16-byte
 // record (slot b at index b), so that a one-round launch fetches them with one
@@ -452,19 +451,25 @@ extern thread_local MgKernelTimer* mg_timer;
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                        \
         }                                                                                               \
     } while (0)
+// MG_LAUNCH (64 lanes per block) of the build whose form word F, a constant in BUILT and KERNEL, equals
+// the run-time `form`; only forms with BUILT true are instantiated. False: no such build (mg_forms.h).
+#define MG_LAUNCH_FORM(BITS, form, BUILT, KERNEL, grid, shmem, stream, ...)                             \
+    mg_with_form<BITS>(form, [&](auto form_) {                                                          \
+        constexpr unsigned F = decltype(form_)::value;                                                  \
+        if constexpr (BUILT) MG_LAUNCH(KERNEL, grid, dim3(64), shmem, stream, __VA_ARGS__);             \
+        return BUILT;                                                                                   \
+    })
 
 // launchers (defined in the .hip files)
 hipError_t mg_launch_render(const MgRenderArgs& A, int nblocks, hipStream_t s);
 hipError_t mg_launch_cube_pick(const mg_cube_pick_args& A, hipStream_t s);
 hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s);
-// k_env_step's contact-moment builds (mg_env_sens.hip): maxl / attr name the build
-void mg_launch_env_step_sens(int maxl, int attr, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
-// k_env_step's reporting builds (mg_env_crep.hip): sens: with the contact moment
-void mg_launch_env_step_crep(int maxl, int attr, int sens, int blocks, hipStream_t s, const MgStep& P,
-                             const MgEnvArgs& A);
-// the joint-friction builds (mg_env_jfr.hip): k_env_step by maxl, k_artic_lanes by A's size
-void mg_launch_env_step_jfr(int maxl, int blocks, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
-void mg_launch_artic_lanes_jfr(hipStream_t s, const MgStep& P, const MgArticArgs& A);
+// the k_env_step<maxl, .., form> / k_artic_lanes builds of the other objects (mg_forms.h
+// k_env_step_object: contact moments, reporting, joint friction); hipErrorNotSupported: not one of its builds
+hipError_t mg_launch_env_step_sens(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_env_step_crep(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_env_step_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_artic_lanes_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgArticArgs& A);
 hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s);

@@ -284,8 +284,10 @@ __device__ __forceinline__ void pair_constants(PileLds& S, const PairHdr& H) {
 // CREP: the reporting build, launched while contact reporting
 // is on: the last substep's points go to the env's staging record, point order
 // (pair order, then the pair's own), with the impulses the force pass sums.
-template <bool CREP>
+template <unsigned F>
 __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
+    static_assert(k_pile_step_built(F), "not a build of k_pile_step (mg_forms.h)");
+    constexpr bool CREP = F & PF_CREP;
     __shared__ PileLds S;
     const int ln = threadIdx.x;
     const int* ei = A.pile_i + (size_t)blockIdx.x * MG_PILE_I_N;
@@ -668,7 +670,7 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
 
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s) {
     if (A.ne <= 0) return hipSuccess;
-    if (A.crep) MG_LAUNCH(k_pile_step<true>, dim3(A.ne), dim3(64), 0, s, P, A);
-    else MG_LAUNCH(k_pile_step<false>, dim3(A.ne), dim3(64), 0, s, P, A);
-    return hipGetLastError();
+    const bool ok = MG_LAUNCH_FORM(PF_BITS, k_pile_step_form(A.crep), k_pile_step_built(F), k_pile_step<F>,
+                                   dim3(A.ne), 0, s, P, A);
+    return ok ? hipGetLastError() : hipErrorNotSupported;
 }

@@ -1214,18 +1214,15 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
 // budget, same-box A/B, profiles/r05_ab_rigid_shape_regs.jsonl). The general
 // ground basis needs more registers: two waves. So do the reporting builds
 // (CREP): at three waves their staging stores spilled 25 to 47 registers.
-#ifndef MG_RIGID1_ROUND_WAVES
-#define MG_RIGID1_ROUND_WAVES 2
-#endif
-#ifndef MG_RIGID1_WIDE_WAVES
-#define MG_RIGID1_WIDE_WAVES 3
-#endif
-// BOX (one-round launches with the slot record whose shapes are all plain
+// (MG_RIGID1_ROUND_WAVES = 2, MG_RIGID1_WIDE_WAVES = 3: mg_forms.h.) BOX (one-round launches with the slot record whose shapes are all plain
 // boxes, MgRigidArgs::box_only): the candidates are compiled for the box alone.
-template <bool UPZ, bool LDS_T, bool WIDE, bool ATTR, bool REC = false, bool CREP = false, bool BOX = false>
-__global__ void __launch_bounds__(64, UPZ && WIDE && !CREP ? MG_RIGID1_WIDE_WAVES : (UPZ ? MG_RIGID1_ROUND_WAVES : 2))
+template <unsigned F>
+__global__ void __launch_bounds__(64, (F & RF_UPZ) && (F & RF_WIDE) && !(F & RF_CREP) ? MG_RIGID1_WIDE_WAVES
+                                                                                     : ((F & RF_UPZ) ? MG_RIGID1_ROUND_WAVES : 2))
 k_rigid_step1(MgStep P, MgRigidArgs A) {
-    static_assert(!BOX || (!WIDE && REC), "BOX: a one-round build that reads the slot record");
+    static_assert(k_rigid_step1_built(F), "not a build of k_rigid_step1 (mg_forms.h)");
+    constexpr bool UPZ = F & RF_UPZ, LDS_T = F & RF_LDS, WIDE = F & RF_WIDE, ATTR = F & RF_ATTR, REC = F & RF_REC,
+                   CREP = F & RF_CREP, BOX = F & RF_BOX;
     extern __shared__ float s_trec[];
     const int i = (WIDE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 64 + threadIdx.x;
     RSTAMP(0);
@@ -1481,8 +1478,10 @@ k_rigid_step1(MgStep P, MgRigidArgs A) {
     }
 }
 
-template <bool UPZ, int MAXC, bool MULTI, bool ATTR, bool CREP = false>
+template <unsigned F, int MAXC, bool MULTI>
 __global__ void __launch_bounds__(64) k_rigid_step(MgStep P, MgRigidArgs A) {
+    static_assert(k_rigid_step_built(F, MAXC, MULTI), "not a build of k_rigid_step (mg_forms.h)");
+    constexpr bool UPZ = F & RF_UPZ, ATTR = F & RF_ATTR, CREP = F & RF_CREP;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A.nf) return;
     const int b = A.free_ids ? A.free_ids[i] : i;
@@ -1544,91 +1543,28 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         A2.crep_n = A.crep_n ? A.crep_n + A.nf1 : nullptr;
         A2.crep_body = A.crep_body ? A.crep_body + A.nf1 : nullptr;
     }
-    if (A.crep) {
-        // contact reporting is on: the reporting builds (template records read
-        // from global memory, the slot's indices from their separate arrays:
-        // where they live changes no value)
-        const bool at = A.attr_idx != nullptr;
-        A1.slot_rec = nullptr;
-        if (A1.nf > 0) {
-            const int blocks = (A1.nf + 63) / 64;
-            // the threshold of the plain launches, kept on purpose although the wide
-            // reporting build holds two waves per SIMD, not three: which bodies
-            // step in which form (and so every value) is then the same with
-            // reporting on and off
-            const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
-            if (form) *form = wide ? MG_RIGID_FORM_WIDE : 0;
-#define MG_K1C(U, W, T) MG_LAUNCH((k_rigid_step1<U, false, W, T, false, true>), dim3(blocks), dim3(64), 0, s, P, A1)
-#define MG_K1C_T(U, W) do { if (at) MG_K1C(U, W, true); else MG_K1C(U, W, false); } while (0)
-            if (upz && wide) MG_K1C_T(true, true);
-            else if (upz) MG_K1C_T(true, false);
-            else if (wide) MG_K1C_T(false, true);
-            else MG_K1C_T(false, false);
-#undef MG_K1C_T
-#undef MG_K1C
-        }
-        if (A2.nf > 0) {
-            const int blocks = (A2.nf + 63) / 64;
-#define MG_K2C(U, T) MG_LAUNCH((k_rigid_step<U, MG_MAX_CONTACTS, true, T, true>), dim3(blocks), dim3(64), 0, s, P, A2)
-            if (upz && at) MG_K2C(true, true);
-            else if (upz) MG_K2C(true, false);
-            else if (at) MG_K2C(false, true);
-            else MG_K2C(false, false);
-#undef MG_K2C
-        }
-        return hipGetLastError();
-    }
+    // which builds run: mg_forms.h (k_rigid_step1_form, k_rigid_step_form)
+    if (A.crep) A1.slot_rec = nullptr;
+    bool ok = true;
     if (A1.nf > 0) {
-        const int blocks = (A1.nf + 63) / 64;
-        // wide: more waves than one resident round (4 SIMDs x 3 or 2 waves per
-        // CU). Such a launch is issue-bound, not latency-bound: it dispatches
+        // a wide launch is issue-bound, not latency-bound: it dispatches
         // longest-first (back to front: the free-body order, migym_capi.cpp) and
         // solves with the scalar rows (tgs_z's packed pairs are fewer
         // instructions for a wave alone on its SIMD, but each holds the issue
         // slots of two scalar ones when waves share it: DESIGN.md §3.2).
-        const bool wide = blocks > mg_cu_count() * 4 * (upz ? MG_RIGID1_ROUND_WAVES : 2);
+        const int blocks = (A1.nf + 63) / 64;
         const size_t lds = (size_t)A.ntb * MG_TREC_N * sizeof(float);
-        // a one-round launch with the packed slot record: the builds that read it
-        // (REC; the others keep the four index arrays in their argument registers)
-        const bool rec = A1.slot_rec != nullptr;
-        // the box-only build (candidates compiled for the box alone): a one-round
-        // launch with the slot record over a z-up ground, its template records
-        // staged in LDS, no attractor, every shape a plain box
-        const bool box = upz && !wide && rec && !A1.attr_idx && lds <= MG_TREC_LDS_MAX && A.box_only;
-        if (form) *form = wide ? MG_RIGID_FORM_WIDE : (rec ? MG_RIGID_FORM_REC : 0) | (box ? MG_RIGID_FORM_BOX : 0);
-#define MG_K1(U, L) \
-    do { \
-        if (wide) MG_LAUNCH((k_rigid_step1<U, L, true, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
-        else if (rec) MG_LAUNCH((k_rigid_step1<U, L, false, false, true>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
-        else MG_LAUNCH((k_rigid_step1<U, L, false, false>), dim3(blocks), dim3(64), L ? lds : 0, s, P, A1); \
-    } while (0)
-        if (A1.attr_idx) {
-            // a free body owns an attractor: the attractor-aware builds (template
-            // records read from global memory: where they live changes no value)
-            if (upz && wide) MG_LAUNCH((k_rigid_step1<true, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-            else if (upz && rec) MG_LAUNCH((k_rigid_step1<true, false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-            else if (upz) MG_LAUNCH((k_rigid_step1<true, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-            else if (wide) MG_LAUNCH((k_rigid_step1<false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-            else if (rec) MG_LAUNCH((k_rigid_step1<false, false, false, true, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-            else MG_LAUNCH((k_rigid_step1<false, false, false, true>), dim3(blocks), dim3(64), 0, s, P, A1);
-        } else if (box) {
-            MG_LAUNCH((k_rigid_step1<true, true, false, false, true, false, true>), dim3(blocks), dim3(64), lds, s, P, A1);
-        } else if (lds <= MG_TREC_LDS_MAX) {
-            if (upz) MG_K1(true, true);
-            else MG_K1(false, true);
-        } else {
-            if (upz) MG_K1(true, false);
-            else MG_K1(false, false);
-        }
-#undef MG_K1
+        const unsigned f = k_rigid_step1_form(upz, blocks, mg_cu_count(), lds, A.slot_rec, A.attr_idx, A.crep,
+                                              A.free_ids, A.box_only);
+        if (form) *form = mg_rigid_form_public(f);
+        ok = MG_LAUNCH_FORM(RF_BITS, f, k_rigid_step1_built(F), k_rigid_step1<F>, dim3(blocks), (F & RF_LDS) ? lds : 0,
+                            s, P, A1);
     }
     if (A2.nf > 0) {
         const int blocks = (A2.nf + 63) / 64;
-        if (A2.attr_idx) {
-            if (upz) MG_LAUNCH((k_rigid_step<true, MG_MAX_CONTACTS, true, true>), dim3(blocks), dim3(64), 0, s, P, A2);
-            else MG_LAUNCH((k_rigid_step<false, MG_MAX_CONTACTS, true, true>), dim3(blocks), dim3(64), 0, s, P, A2);
-        } else if (upz) MG_LAUNCH((k_rigid_step<true, MG_MAX_CONTACTS, true, false>), dim3(blocks), dim3(64), 0, s, P, A2);
-        else MG_LAUNCH((k_rigid_step<false, MG_MAX_CONTACTS, true, false>), dim3(blocks), dim3(64), 0, s, P, A2);
+        ok = MG_LAUNCH_FORM(RF_BITS, k_rigid_step_form(upz, A.attr_idx, A.crep),
+                            k_rigid_step_built(F, MG_MAX_CONTACTS, true), (k_rigid_step<F, MG_MAX_CONTACTS, true>),
+                            dim3(blocks), 0, s, P, A2) && ok;
     }
-    return hipGetLastError();
+    return ok ? hipGetLastError() : hipErrorNotSupported;
 }

@@ -900,6 +900,186 @@ static MgSensorArgs sensor_args(const mg_sim* s, const MgStep& P) {
     A.inv_dt = P.inv_dt;
     return A;
 }
+// This sim's step may write its rows itself (the fused refresh, the host stage): every kernel
+// that steps a body writes its rows, none is an attractor, reporting or joint-friction build.
+static bool step_writes_rows(const mg_sim* s) {
+    return s->layout.step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0;
+}
+
+// Where the step kernels write the refreshed rows themselves: the bound tensors
+// (MG_FUSE_STEP_OUT) or the host stage (mg_fetch_host_state), each optional; all null: nowhere.
+struct StepOut {
+    float *rb = nullptr, *root = nullptr, *dof = nullptr;
+    const int *out_body = nullptr, *out_root_row = nullptr;   // internal slot -> global body / actor row (or -1)
+};
+
+// The DOF force rows of a launch, or null: written while the sim reports DOF forces, and by every
+// contact-moment, reporting and joint-friction build (`feature`; the refresh masks the other rows).
+static float* dof_frc_rows(const mg_sim* s, bool feature) {
+    return s->dof_frc_n > 0 || feature ? s->d_dof_frc : nullptr;
+}
+
+// Group gi's launch over its plain instances (who 0), over those that hold a friction DOF (1)
+// or own an attractor (2): owners step apart (the group's split rows: the plain instances, then
+// these; rows loaded, not computed; a group with both kinds of owner is refused).
+static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
+    const ArticGroup& g = s->groups[gi];
+    MgArticArgs A{};
+    // the DOF part's validity is a flag in the block (MG_CHAIN_UNI_DOFOK), not
+    // a launch choice: a captured launch follows later set_dof_props
+    A.uni = g.uni_mass ? s->d_chain_uni + gi * MG_CHAIN_UNI_N : nullptr;
+    A.na = g.step_count; A.nb = s->layout.nb; A.nd = s->layout.nd;
+    A.artic_i = s->d_artic_step + (size_t)g.step_offset * MG_ARTIC_I_N;
+    A.aff = g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
+    A.out_aff = g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
+    A.tmpl = g.tmpl; A.nl = g.nl; A.ndof = g.ndof; A.fixed_base = g.fixed_base; A.chain = g.chain; A.nbl = g.nbody;
+    A.link_f = s->d_link_f + (size_t)g.first_link * MG_LINK_F_N;
+    A.link_i = s->d_link_i + (size_t)g.first_link * MG_LINK_I_N;
+    A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
+    A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
+    A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
+    fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
+    A.dof_props = s->d_dof_props;
+    A.ext = s->ext_pending ? s->d_ext : nullptr;
+    A.cforce = s->d_cforce;
+    A.dof_frc = dof_frc_rows(s, false);
+    A.out_rb = O.rb; A.out_root = O.root; A.out_dof = O.dof;   // chain groups only (s->layout.step_out_ok)
+    A.out_body = O.out_body; A.out_root_row = O.out_root_row;
+    if (g.attr_count > 0 || g.jfr_count > 0) {
+        const int* split = g.jfr_count > 0 ? s->d_artic_jsplit : s->d_artic_split;
+        A.artic_i = split + (size_t)g.step_offset * MG_ARTIC_I_N;
+        A.na = g.jfr_count > 0 ? g.jfr_plain : g.plain_count;
+        A.aff = 0;
+        A.out_aff = 0;
+    }
+    if (who != 0) A.uni = nullptr;
+    if (who == 1) {
+        A.artic_i += (size_t)g.jfr_plain * MG_ARTIC_I_N;
+        A.na = g.jfr_count;
+        A.jfr = 1;
+        A.dof_frc = dof_frc_rows(s, true);
+    } else if (who == 2) {
+        A.artic_i += (size_t)g.plain_count * MG_ARTIC_I_N;
+        A.na = g.attr_count;
+        A.attr_idx = s->d_attr_idx;
+        A.attr = s->d_attr;
+    }
+    return A;
+}
+
+// the coupled step of one env group (mg_env.hip)
+static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g) {
+    MgEnvArgs A{};
+    A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
+    A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
+    A.pairs = s->d_pairs;
+    A.fpatch = s->d_fpatch;
+    A.fp_mask = s->d_fp_mask + (size_t)g.offset * MG_FP_W;
+    A.carry = s->d_env_carry + (size_t)g.offset * mg_env_carry_floats();
+    A.ctab = s->d_env_ctab + (size_t)g.offset * mg_env_ctab_floats();
+    A.nl = g.tmpl >= 0 ? g.nl : 0;
+    A.ndof = g.tmpl >= 0 ? g.ndof : 0;
+    A.floating = g.tmpl >= 0 ? g.floating : 0;
+    A.max_free = g.max_free;
+    A.link_f = s->d_link_f + (size_t)(g.tmpl >= 0 ? g.first_link : 0) * MG_LINK_F_N;
+    A.link_i = s->d_link_i + (size_t)(g.tmpl >= 0 ? g.first_link : 0) * MG_LINK_I_N;
+    A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
+    A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
+    A.shape_obb = s->d_shape_obb;
+    A.nhull = s->layout.nhull_floats;
+    A.nshape = s->layout.ns;
+    A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
+    A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
+    fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
+    A.dof_props = s->d_dof_props;
+    A.ext = s->ext_pending ? s->d_ext : nullptr;
+    A.cforce = s->d_cforce;
+    // joint friction: attractors, sensors and reporting on this group were refused
+    A.jfr = g.jfr ? 1 : 0;
+    if (s->n_attr_env > 0 && !g.jfr) {
+        A.attr_idx = s->d_attr_idx;
+        A.attr = s->d_attr;
+    }
+    if (s->crep_on) {   // the reporting builds
+        A.crep = s->d_crep_cenv + g.offset;
+        A.crep_n = s->d_crep_cenv_n + g.offset;
+        A.crep_body = s->d_slot_global;
+        A.crep_stride = std::max(s->layout.n_coupled, 1);
+    }
+    // the contact-moment builds
+    if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) A.ctorque = s->d_ctorque;
+    A.dof_frc = dof_frc_rows(s, A.crep || A.ctorque || A.jfr);
+    return A;
+}
+
+static MgPileArgs pile_args(const mg_sim* s) {
+    MgPileArgs A{};
+    A.ne = s->layout.n_pile; A.nb = s->layout.nb;
+    A.pile_i = s->d_pile_i; A.pile_body = s->d_pile_body; A.pairs = s->d_pile_pairs; A.slots = s->d_pile_slots;
+    A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
+    A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
+    A.ext = s->ext_pending ? s->d_ext : nullptr;
+    A.cforce = s->d_cforce;
+    if (s->crep_on) {   // the reporting build
+        A.crep = s->d_crep_pile;
+        A.crep_n = s->d_crep_pile_n;
+        A.crep_body = s->d_slot_global;
+    }
+    return A;
+}
+
+// the free-body step; a deferred root set (s->pend_root) is read by the kernel
+static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
+    MgRigidArgs A{};
+    A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
+    A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
+    A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
+    A.trec = s->d_trec; A.ntb = s->layout.ntb;
+    A.slot_rec = s->d_slot_rec;
+    A.box_only = s->layout.free_flags.empty() ? 0 : s->layout.free_flags[0];
+    A.gpatch = s->d_gpatch;
+    A.gstride = std::max(s->layout.nf1, 1);
+    A.ext = s->ext_pending ? s->d_ext : nullptr;
+    A.cforce = s->d_cforce;
+    if (s->n_attr_free > 0) {
+        A.attr_idx = s->d_attr_idx;
+        A.attr = s->d_attr;
+    }
+    if (s->crep_on) {   // the reporting builds
+        A.crep = s->d_crep_free;
+        A.crep_n = s->d_crep_free_n;
+        A.crep_body = s->d_slot_global;
+        A.crep_stride = std::max(s->layout.nf_rigid, 1);
+    }
+    if (s->pend_root) {
+        A.root_src = s->pend_root;
+        A.root_row = s->d_root_row;
+    }
+    A.out_rb = O.rb; A.out_root = O.root;
+    A.out_body = O.out_body; A.out_root_row = O.out_root_row;
+    return A;
+}
+
+// the contact list of a frame: the staging records packed in owner order
+static MgContactArgs contact_args(const mg_sim* s) {
+    const int n[MG_CREP_FAMILIES] = {s->layout.nf_rigid, s->layout.n_coupled, s->layout.n_pile};
+    const int cap[MG_CREP_FAMILIES] = {MG_CREP_FREE_CAP, 2 * MG_ENV_MAXCT_WIDE, MG_PILE_MAXPT};
+    const float* stage[MG_CREP_FAMILIES] = {s->d_crep_free, s->d_crep_cenv, s->d_crep_pile};
+    const int* count[MG_CREP_FAMILIES] = {s->d_crep_free_n, s->d_crep_cenv_n, s->d_crep_pile_n};
+    MgContactArgs C{};
+    for (int k = 0; k < MG_CREP_FAMILIES; ++k) {
+        C.fam[k] = {n[k], cap[k], std::max(n[k], 1), stage[k], count[k], s->d_crep_env + C.n_own, nullptr};
+        C.n_own += n[k];
+    }
+    C.fam[1].col = s->d_crep_col;
+    C.nblk = (C.n_own + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK;
+    C.blk_sum = s->d_crep_blk;
+    C.out = s->d_crep_out;
+    C.capacity = s->crep_capacity;
+    C.header = s->d_crep_hdr;
+    C.header_host = s->d_crep_hdr_alias;
+    return C;
+}
 
 int32_t mg_simulate(mg_sim* s, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "simulate before the model was uploaded");
@@ -962,194 +1142,43 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         HIP_TRY(mg_launch_sensor_mark(sensor_args(s, P), st));
     }
     const unsigned long long step_cid = capture_id(st);
-    const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && s->layout.step_out_ok &&
-                          s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 &&
+    StepOut O;
+    const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && step_writes_rows(s) &&
                           (s->bind_root || s->bind_rb || s->bind_dof);
     // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
     // write into the library's own buffer, so no caller-visible tensor changes
     float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && s->layout.step_out_ok && s->attrs.empty() && !s->crep_on &&
-                          s->jfr_ndof == 0 && step_cid == 0;
-    float* ho_root = host_out ? ho_base : nullptr;
-    float* ho_rb = host_out ? ho_base + (size_t)s->layout.na * MG_STATE_N : nullptr;
-    float* ho_dof = host_out && s->layout.nd ? ho_base + (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N : nullptr;
+    const bool host_out = !step_out && ho_base && step_writes_rows(s) && step_cid == 0;
+    if (step_out)
+        O = {s->bind_rb, s->bind_root, s->bind_dof, s->d_slot_global, s->d_slot_actor};
+    else if (host_out)
+        O = {ho_base + (size_t)s->layout.na * MG_STATE_N, ho_base,
+             s->layout.nd ? ho_base + (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N : nullptr, s->d_slot_global,
+             s->d_slot_actor};
     for (size_t gi = 0; gi < s->groups.size(); ++gi) {
         const ArticGroup& g = s->groups[gi];
         if (g.step_count == 0) continue;
-        MgArticArgs A{};
-        // the DOF part's validity is a flag in the block (MG_CHAIN_UNI_DOFOK), not
-        // a launch choice: a captured launch follows later set_dof_props
-        A.uni = g.uni_mass ? s->d_chain_uni + gi * MG_CHAIN_UNI_N : nullptr;
-        A.na = g.step_count; A.nb = s->layout.nb; A.nd = s->layout.nd;
-        A.artic_i = s->d_artic_step + (size_t)g.step_offset * MG_ARTIC_I_N;
-        A.aff = g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
-        A.out_aff = g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
-        A.tmpl = g.tmpl; A.nl = g.nl; A.ndof = g.ndof; A.fixed_base = g.fixed_base; A.chain = g.chain; A.nbl = g.nbody;
-        A.link_f = s->d_link_f + (size_t)g.first_link * MG_LINK_F_N;
-        A.link_i = s->d_link_i + (size_t)g.first_link * MG_LINK_I_N;
-        A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
-        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
-        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
-        fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
-        A.dof_props = s->d_dof_props;
-        A.ext = s->ext_pending ? s->d_ext : nullptr;
-        A.cforce = s->d_cforce;
-        A.dof_frc = s->dof_frc_n > 0 ? s->d_dof_frc : nullptr;
-        if (step_out || host_out) {   // chain groups only (s->layout.step_out_ok)
-            A.out_rb = step_out ? s->bind_rb : ho_rb;
-            A.out_root = step_out ? s->bind_root : ho_root;
-            A.out_dof = step_out ? s->bind_dof : ho_dof;
-            A.out_body = s->d_slot_global;
-            A.out_root_row = s->d_slot_actor;
-        }
-        if (g.attr_count > 0) {
-            // instances that own an attractor step apart (the group's split rows:
-            // the plain instances, then these), rows loaded, not computed
-            A.artic_i = s->d_artic_split + (size_t)g.step_offset * MG_ARTIC_I_N;
-            A.na = g.plain_count;
-            A.aff = 0;
-            A.out_aff = 0;
-        }
-        if (g.jfr_count > 0) {
-            // instances that hold a friction DOF step apart too (their own split
-            // rows; a group with both kinds of owner was refused above)
-            A.artic_i = s->d_artic_jsplit + (size_t)g.step_offset * MG_ARTIC_I_N;
-            A.na = g.jfr_plain;
-            A.aff = 0;
-            A.out_aff = 0;
-        }
-        hipError_t e = mg_launch_artic_step(P, A, st);
-        if (e != hipSuccess) return fail(MG_ERR_DEVICE, "articulation step launch: %s", hipGetErrorString(e));
-        if (g.jfr_count > 0) {
-            MgArticArgs B = A;
-            B.artic_i = A.artic_i + (size_t)g.jfr_plain * MG_ARTIC_I_N;
-            B.na = g.jfr_count;
-            B.uni = nullptr;
-            B.jfr = 1;
-            B.dof_frc = s->d_dof_frc;   // the joint-friction build reports forces too
-            e = mg_launch_artic_step(P, B, st);
+        const bool on[3] = {true, g.jfr_count > 0, g.attr_count > 0};
+        const char* const who[3] = {"", " (joint friction)", " (attractors)"};
+        for (int k = 0; k < 3; ++k) {
+            if (!on[k]) continue;
+            hipError_t e = mg_launch_artic_step(P, artic_args(s, gi, O, k), st);
             if (e != hipSuccess)
-                return fail(MG_ERR_DEVICE, "articulation step launch (joint friction): %s", hipGetErrorString(e));
-        }
-        if (g.attr_count > 0) {
-            MgArticArgs B = A;
-            B.artic_i = A.artic_i + (size_t)g.plain_count * MG_ARTIC_I_N;
-            B.na = g.attr_count;
-            B.uni = nullptr;
-            B.attr_idx = s->d_attr_idx;
-            B.attr = s->d_attr;
-            e = mg_launch_artic_step(P, B, st);
-            if (e != hipSuccess)
-                return fail(MG_ERR_DEVICE, "articulation step launch (attractors): %s", hipGetErrorString(e));
+                return fail(MG_ERR_DEVICE, "articulation step launch%s: %s", who[k], hipGetErrorString(e));
         }
     }
     for (const EnvGroup& g : s->env_groups) {
-        MgEnvArgs A{};
-        A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
-        A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
-        A.pairs = s->d_pairs;
-        A.fpatch = s->d_fpatch;
-        A.fp_mask = s->d_fp_mask + (size_t)g.offset * MG_FP_W;
-        A.carry = s->d_env_carry + (size_t)g.offset * mg_env_carry_floats();
-        A.ctab = s->d_env_ctab + (size_t)g.offset * mg_env_ctab_floats();
-        A.nl = g.tmpl >= 0 ? g.nl : 0;
-        A.ndof = g.tmpl >= 0 ? g.ndof : 0;
-        A.floating = g.tmpl >= 0 ? g.floating : 0;
-        A.max_free = g.max_free;
-        A.link_f = s->d_link_f + (size_t)(g.tmpl >= 0 ? g.first_link : 0) * MG_LINK_F_N;
-        A.link_i = s->d_link_i + (size_t)(g.tmpl >= 0 ? g.first_link : 0) * MG_LINK_I_N;
-        A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
-        A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
-        A.shape_obb = s->d_shape_obb;
-        A.nhull = s->layout.nhull_floats;
-        A.nshape = s->layout.ns;
-        A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
-        A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
-        fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
-        A.dof_props = s->d_dof_props;
-        A.ext = s->ext_pending ? s->d_ext : nullptr;
-        A.cforce = s->d_cforce;
-        A.dof_frc = s->dof_frc_n > 0 ? s->d_dof_frc : nullptr;
-        if (s->n_attr_env > 0) {
-            A.attr_idx = s->d_attr_idx;
-            A.attr = s->d_attr;
-        }
-        if (s->crep_on) {
-            // the reporting builds, force-reporting builds too
-            A.crep = s->d_crep_cenv + g.offset;
-            A.crep_n = s->d_crep_cenv_n + g.offset;
-            A.crep_body = s->d_slot_global;
-            A.crep_stride = std::max(s->layout.n_coupled, 1);
-            A.dof_frc = s->d_dof_frc;
-        }
-        if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) {
-            // the contact-moment builds, which are force-reporting builds too
-            // (rows of DOFs that do not report are masked by the refresh)
-            A.ctorque = s->d_ctorque;
-            A.dof_frc = s->d_dof_frc;
-        }
-        if (g.jfr) {
-            // the joint-friction builds, force-reporting builds too; attractors,
-            // sensors and reporting on this group were refused above
-            A.jfr = 1;
-            A.attr_idx = nullptr;
-            A.attr = nullptr;
-            A.dof_frc = s->d_dof_frc;
-        }
-        hipError_t e = mg_launch_env_step(P, A, st);
+        hipError_t e = mg_launch_env_step(P, env_args(s, g), st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
     }
     if (s->layout.n_pile > 0) {
-        MgPileArgs A{};
-        A.ne = s->layout.n_pile; A.nb = s->layout.nb;
-        A.pile_i = s->d_pile_i; A.pile_body = s->d_pile_body; A.pairs = s->d_pile_pairs; A.slots = s->d_pile_slots;
-        A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
-        A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
-        A.ext = s->ext_pending ? s->d_ext : nullptr;
-        A.cforce = s->d_cforce;
-        if (s->crep_on) {   // the reporting build
-            A.crep = s->d_crep_pile;
-            A.crep_n = s->d_crep_pile_n;
-            A.crep_body = s->d_slot_global;
-        }
-        hipError_t e = mg_launch_pile_step(P, A, st);
+        hipError_t e = mg_launch_pile_step(P, pile_args(s), st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
     }
     if (s->layout.nf_rigid > 0) {
-        MgRigidArgs A{};
-        A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
-        A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
-        A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
-        A.trec = s->d_trec; A.ntb = s->layout.ntb;
-        A.slot_rec = s->d_slot_rec;
-        A.box_only = s->layout.free_flags.empty() ? 0 : s->layout.free_flags[0];
-        A.gpatch = s->d_gpatch;
-        A.gstride = std::max(s->layout.nf1, 1);
-        A.ext = s->ext_pending ? s->d_ext : nullptr;
-        A.cforce = s->d_cforce;
-        if (s->n_attr_free > 0) {
-            A.attr_idx = s->d_attr_idx;
-            A.attr = s->d_attr;
-        }
-        if (s->crep_on) {   // the reporting builds
-            A.crep = s->d_crep_free;
-            A.crep_n = s->d_crep_free_n;
-            A.crep_body = s->d_slot_global;
-            A.crep_stride = std::max(s->layout.nf_rigid, 1);
-        }
-        bool reads_root_in = false;
-        if (s->pend_root) {   // the deferred root set, read by the step kernel
-            A.root_src = s->pend_root;
-            A.root_row = s->d_root_row;
-            reads_root_in = s->pend_root == s->d_root_in_alias;
-            s->pend_root = nullptr;
-        }
-        if (step_out || host_out) {
-            A.out_rb = step_out ? s->bind_rb : ho_rb;
-            A.out_root = step_out ? s->bind_root : ho_root;
-            A.out_body = s->d_slot_global;     // internal slot -> global body
-            A.out_root_row = s->d_slot_actor;
-        }
+        const MgRigidArgs A = rigid_args(s, O);
+        const bool reads_root_in = s->pend_root && s->pend_root == s->d_root_in_alias;
+        s->pend_root = nullptr;   // the deferred root set: read by the step kernel
         HIP_TRY(mg_launch_rigid_step(P, A, st, &s->rigid_form));
         if (reads_root_in) {
             HIP_TRY(hipEventRecord(s->root_ev, st));
@@ -1167,7 +1196,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         s->ho_written = ho_base;
         s->ho_root_gen = s->state_gen;
         s->ho_rb_gen = s->state_gen;
-        s->ho_dof_gen = ho_dof ? s->dof_sgen : -1;
+        s->ho_dof_gen = O.dof ? s->dof_sgen : -1;
     }
     if (step_out) {
         if (s->bind_root) { s->out_gen = s->state_gen; s->out_cap = step_cid; }
@@ -1175,35 +1204,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         if (s->bind_dof) { s->dof_gen = s->dof_sgen; s->dof_cap = step_cid; }
     }
     if (s->crep_on) {
-        // the contact list of this frame: the staging records packed in owner order
-        MgContactArgs C{};
-        C.fam[0].n = s->layout.nf_rigid;
-        C.fam[0].cap = MG_CREP_FREE_CAP;
-        C.fam[0].stride = std::max(s->layout.nf_rigid, 1);
-        C.fam[0].stage = s->d_crep_free;
-        C.fam[0].count = s->d_crep_free_n;
-        C.fam[0].env = s->d_crep_env;
-        C.fam[1].n = s->layout.n_coupled;
-        C.fam[1].cap = 2 * MG_ENV_MAXCT_WIDE;
-        C.fam[1].stride = std::max(s->layout.n_coupled, 1);
-        C.fam[1].stage = s->d_crep_cenv;
-        C.fam[1].count = s->d_crep_cenv_n;
-        C.fam[1].env = s->d_crep_env + s->layout.nf_rigid;
-        C.fam[1].col = s->d_crep_col;
-        C.fam[2].n = s->layout.n_pile;
-        C.fam[2].cap = MG_PILE_MAXPT;
-        C.fam[2].stride = std::max(s->layout.n_pile, 1);
-        C.fam[2].stage = s->d_crep_pile;
-        C.fam[2].count = s->d_crep_pile_n;
-        C.fam[2].env = s->d_crep_env + s->layout.nf_rigid + s->layout.n_coupled;
-        C.n_own = s->layout.nf_rigid + s->layout.n_coupled + s->layout.n_pile;
-        C.nblk = (C.n_own + MG_CREP_BLOCK - 1) / MG_CREP_BLOCK;
-        C.blk_sum = s->d_crep_blk;
-        C.out = s->d_crep_out;
-        C.capacity = s->crep_capacity;
-        C.header = s->d_crep_hdr;
-        C.header_host = s->d_crep_hdr_alias;
-        HIP_TRY(mg_launch_contact_compact(C, st));
+        HIP_TRY(mg_launch_contact_compact(contact_args(s), st));
         s->crep_valid = true;
     }
     // the force sensors' readings, before the applied wrenches are cleared
