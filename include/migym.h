@@ -509,6 +509,45 @@ int32_t     mg_contact_reporting(mg_sim* sim);              /* 0 / 1 */
 int32_t     mg_refresh_rigid_contacts(mg_sim* sim, mg_rigid_contact* dst, int32_t cap, int32_t dst_host,
                                       int32_t* total, void* stream);
 
+/* ---- contact capacity report ------------------------------
+ * Three step kernels keep their contacts in fixed tables and drop what does not
+ * fit: a pile env's active-pair list (128 pairs, 256 points) and its 64 colours,
+ * a coupled env's contact table (16 contacts and 16 anchors, 48 + 48 in a
+ * 64-lane env), a multi-shape free body's 8 ground slots. Every step kernel
+ * counts what it drops, always: MG_CAP_N 64-bit counters per model, cumulative
+ * since the upload or the last reset (graph replays advance them too), and one
+ * sticky flag word (MG_CAPF_* bits) per pile env, coupled env and multi-shape
+ * free body. A step that drops nothing touches neither.
+ *
+ * mg_capacity_stats: the counters into out; reset != 0 then zeroes the counters
+ * and the flag words on `stream`. mg_capacity_env_flags: the flag words OR-ed per
+ * env into dst_host[n_envs] (n_envs: the model's env count). Both wait for
+ * `stream`, make one copy and no launch, and are refused (MG_ERR_STATE) while
+ * `stream` is being captured. mg_capacity_tracked: 1 when the model holds a pile
+ * env, a coupled env or a multi-shape free body (nothing else can drop a
+ * contact), else 0. */
+#define MG_CAP_PILE_OVERFLOW            0   /* pile env-substeps whose active-pair list ended early */
+#define MG_CAP_PILE_OVER_PAIRS          1   /* ... the refused pair would have passed 128 active pairs */
+#define MG_CAP_PILE_OVER_POINTS         2   /* ... it would have passed 256 points (both may hold) */
+#define MG_CAP_PILE_UNCOLOURED          3   /* active pairs that found all 64 colours taken (never solved) */
+#define MG_CAP_PILE_UNVISITED           4   /* active pairs the colouring's loop bound left out (expected 0) */
+#define MG_CAP_ENV_OVERFLOW             5   /* coupled env-substeps with contacts or anchors past the table */
+#define MG_CAP_ENV_CONTACTS_DROPPED     6   /* sum of max(0, contacts found - table size) */
+#define MG_CAP_ENV_ANCHORS_DROPPED      7   /* sum of max(0, anchors found - table size) */
+#define MG_CAP_RIGID_OVERFLOW           8   /* multi-shape free body-substeps with a candidate past the 8 slots */
+#define MG_CAP_RIGID_CANDIDATES_DROPPED 9   /* those candidates */
+#define MG_CAP_N                        10
+#define MG_CAPF_PILE_PAIRS      1
+#define MG_CAPF_PILE_POINTS     2
+#define MG_CAPF_PILE_COLOURS    4
+#define MG_CAPF_PILE_UNVISITED  8
+#define MG_CAPF_ENV_CONTACTS    16
+#define MG_CAPF_ENV_ANCHORS     32
+#define MG_CAPF_RIGID_SLOTS     64
+int32_t     mg_capacity_stats(mg_sim* sim, int64_t out[MG_CAP_N], int32_t reset, void* stream);
+int32_t     mg_capacity_env_flags(mg_sim* sim, int32_t* dst_host, int32_t n_envs, void* stream);
+int32_t     mg_capacity_tracked(mg_sim* sim);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /

@@ -147,6 +147,19 @@ RIGID_CONTACT_DTYPE = np.dtype([
 ])
 MG_RENDER_MAX_SHAPES = 64
 
+# contact capacity report (include/migym.h): counter names by
+# index (MG_CAP_*), flag names by bit (MG_CAPF_*)
+MG_ERR_ARG, MG_ERR_DEVICE, MG_ERR_STATE, MG_ERR_UNSUPPORTED = -1, -2, -3, -4
+CAPACITY_COUNTERS = (
+    "PILE_OVERFLOW", "PILE_OVER_PAIRS", "PILE_OVER_POINTS", "PILE_UNCOLOURED", "PILE_UNVISITED",
+    "ENV_OVERFLOW", "ENV_CONTACTS_DROPPED", "ENV_ANCHORS_DROPPED",
+    "RIGID_OVERFLOW", "RIGID_CANDIDATES_DROPPED",
+)
+MG_CAP_N = len(CAPACITY_COUNTERS)
+CAPACITY_FLAGS = (
+    "PILE_PAIRS", "PILE_POINTS", "PILE_COLOURS", "PILE_UNVISITED", "ENV_CONTACTS", "ENV_ANCHORS", "RIGID_SLOTS",
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -221,6 +234,9 @@ def _load():
         "mg_contact_reporting": (i32, [vp]),
         "mg_refresh_rigid_contacts": (i32, [vp, vp, i32, i32, vp, vp]),
         "mg_joint_friction_stats": (i32, [vp, vp]),
+        "mg_capacity_stats": (i32, [vp, vp, i32, vp]),
+        "mg_capacity_env_flags": (i32, [vp, vp, i32, vp]),
+        "mg_capacity_tracked": (i32, [vp]),
         "mg_debug_plan_layout": (vp, [ctypes.POINTER(MgSimParams), ctypes.POINTER(MgModel)]),
         "mg_debug_layout_table": (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]),
         "mg_debug_free_layout": (None, [vp]),
@@ -254,6 +270,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_force_sensors", "mg_refresh_force_sensor", "mg_num_force_sensors",
     "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
     "mg_joint_friction_stats",
+    "mg_capacity_stats", "mg_capacity_env_flags", "mg_capacity_tracked",
     "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
     "mg_last_rigid_form",
 )

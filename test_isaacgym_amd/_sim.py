@@ -273,6 +273,13 @@ class Sim:
         self.contact_reporting = (False, 0)
         self.contact_reporting_dirty = False
         self.contact_first_query = False
+        # contact capacity report: fetch_results(sim, True)
+        # looks at the counters when the frame count is a power of two
+        # (MIGYM_CAPACITY_CHECK=0 at create_sim: never) and names each kind of
+        # drop on stderr once; capacity_tracked: mg_capacity_tracked, once known
+        self.capacity_check = os.environ.get("MIGYM_CAPACITY_CHECK", "1") != "0"
+        self.capacity_warned = set()
+        self.capacity_tracked = None
 
     @property
     def renderer(self):
@@ -844,6 +851,56 @@ class Sim:
         N.check(N.lib.mg_joint_friction_stats(self.require_native("joint_friction_stats"), out),
                 "mg_joint_friction_stats")
         return tuple(int(v) for v in out)
+
+    def capacity_report(self, reset=False):
+        """gym.get_contact_capacity_report: the counters by name (mg_capacity_stats)
+        and "envs": {env index: [flag names]} of the flagged envs
+        (mg_capacity_env_flags); reset zeroes both after the read."""
+        h = self.require_native("get_contact_capacity_report")
+        cnt = (ctypes.c_int64 * N.MG_CAP_N)()
+        flags = np.zeros(max(len(self.envs), 1), dtype=np.int32)
+        # the flags first: the counters' read may reset both
+        N.check(N.lib.mg_capacity_env_flags(h, flags.ctypes.data, len(self.envs), self.stream()),
+                "mg_capacity_env_flags")
+        N.check(N.lib.mg_capacity_stats(h, cnt, 1 if reset else 0, self.stream()), "mg_capacity_stats")
+        rep = {name: int(cnt[k]) for k, name in enumerate(N.CAPACITY_COUNTERS)}
+        rep["envs"] = {int(e): [name for b, name in enumerate(N.CAPACITY_FLAGS) if flags[e] >> b & 1]
+                       for e in np.nonzero(flags[:len(self.envs)])[0]}
+        return rep
+
+    # flag name -> (what the stderr line calls it, the counter it reports)
+    _CAPACITY_KINDS = {
+        "PILE_PAIRS": ("pile env active-pair cap (128 pairs)", "PILE_OVER_PAIRS"),
+        "PILE_POINTS": ("pile env contact-point cap (256 points)", "PILE_OVER_POINTS"),
+        "PILE_COLOURS": ("pile env colour limit (64 pairs per body)", "PILE_UNCOLOURED"),
+        "PILE_UNVISITED": ("pile env colouring loop bound", "PILE_UNVISITED"),
+        "ENV_CONTACTS": ("coupled env contact table", "ENV_CONTACTS_DROPPED"),
+        "ENV_ANCHORS": ("coupled env friction-anchor table", "ENV_ANCHORS_DROPPED"),
+        "RIGID_SLOTS": ("multi-shape free body ground slots (8)", "RIGID_CANDIDATES_DROPPED"),
+    }
+
+    def capacity_autocheck(self):
+        """The check of fetch_results(sim, True): nothing unless the model holds a
+        kernel that can drop contacts, the frame count is a power of two and the
+        stream is not being captured; each kind of drop is named once per sim."""
+        if not self.capacity_check or self.native is None or self.frame <= 0 or self.frame & (self.frame - 1):
+            return
+        if self.capacity_tracked is None:
+            self.capacity_tracked = bool(N.lib.mg_capacity_tracked(self.native))
+        if not self.capacity_tracked or torch.cuda.is_current_stream_capturing():
+            return
+        cnt = (ctypes.c_int64 * N.MG_CAP_N)()
+        N.check(N.lib.mg_capacity_stats(self.native, cnt, 0, self.stream()), "mg_capacity_stats")
+        if not any(cnt):
+            return
+        rep = self.capacity_report()
+        for flag, (kind, counter) in self._CAPACITY_KINDS.items():
+            envs = sorted(e for e, names in rep["envs"].items() if flag in names)
+            if flag in self.capacity_warned or not envs:
+                continue
+            self.capacity_warned.add(flag)
+            print("*** migym: contact capacity exceeded: %s, %d in %d envs (first env %d): contacts were dropped; "
+                  "see gym.get_contact_capacity_report" % (kind, rep[counter], len(envs), envs[0]), file=sys.stderr)
 
     def require_native(self, what):
         self.finalize()

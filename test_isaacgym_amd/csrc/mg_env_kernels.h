@@ -1488,6 +1488,16 @@ __global__ void __launch_bounds__(64, MG_NP_WAVES) k_env_np(MgStep P, MgEnvArgs 
             ct[2] = ibits(S.link_rows);
             ct[3] = ibits((int)(unsigned)(S.pstart & 0xFFFFFFFFull));
             ct[4] = ibits((int)(unsigned)(S.pstart >> 32));
+            // what the table cannot hold is dropped: base is
+            // every contact the narrow phase found, abase every anchor of the
+            // patches that placed a contact
+            if (base > MAXCT || abase > MAXCT) {
+                mg_cap_add(A.cap, MG_CAP_ENV_OVERFLOW, 1);
+                if (base > MAXCT) mg_cap_add(A.cap, MG_CAP_ENV_CONTACTS_DROPPED, base - MAXCT);
+                if (abase > MAXCT) mg_cap_add(A.cap, MG_CAP_ENV_ANCHORS_DROPPED, abase - MAXCT);
+                atomicOr(A.cap.flags + e,
+                         (base > MAXCT ? MG_CAPF_ENV_CONTACTS : 0) | (abase > MAXCT ? MG_CAPF_ENV_ANCHORS : 0));
+            }
         }
         const int nc = base < MAXCT ? base : MAXCT, na = abase < MAXCT ? abase : MAXCT;
         for (int c = ln; c < nc; c += G) {

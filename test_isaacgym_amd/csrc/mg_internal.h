@@ -35,6 +35,25 @@ struct MgStep {
     float fric_corr;     // friction_correlation_distance
 };
 
+// Contact capacity report (include/migym.h MG_CAP_* /
+// MG_CAPF_*): the model's counters and the flag words of the launch's units
+// (unit u of the launch at flags[u]). Touched only where a kernel drops a
+// contact: a step that drops none executes no atomic.
+struct MgCapArgs {
+    unsigned long long* cnt;   // [MG_CAP_N]
+    int*                flags; // [units of the launch]
+};
+__device__ __forceinline__ void mg_cap_add(const MgCapArgs& C, int k, int n) {
+    atomicAdd(C.cnt + k, (unsigned long long)n);
+}
+// the sum of a small non-negative per-lane value over the wave's active lanes,
+// by ballot and popcount, bit by bit (overflow paths only)
+__device__ __forceinline__ int mg_cap_wave_sum(int v) {
+    int sum = 0;
+    for (int b = 0; b < 20; ++b) sum += __popcll(__ballot((v >> b) & 1)) << b;
+    return sum;
+}
+
 // Compact per-template record of the single-shape free-body kernel (built at
 // upload): the MG_TBODY_F_N template floats, then the template's first shape
 // record (type -1 when it has none). Staged in LDS when the table fits.
@@ -103,6 +122,8 @@ struct MgRigidArgs {
     // with the slot record then runs the build whose candidate search is
     // compiled for that box alone (the BOX build of k_rigid_step1)
     int          box_only;
+    // contact capacity report: the multi-shape launch's unit i = its body i
+    MgCapArgs    cap;
 };
 
 // Rigid contact list (mg_contact.hip). A reporting build of a
@@ -294,6 +315,8 @@ struct MgEnvArgs {
     // friction > 0 (k_env_step's JFR builds; dof_frc set, none of attr, ctorque,
     // crep)
     int          jfr;
+    // contact capacity report: unit e = env e of the launch (counted by k_env_np)
+    MgCapArgs    cap;
 };
 
 // Force sensors (mg_sensor.hip). Lane = one sensor; the lanes
@@ -383,6 +406,8 @@ struct MgPileArgs {
     float*       crep;
     int*         crep_n;      // [ne]
     const int*   crep_body;   // [nb]
+    // contact capacity report: unit e = pile env e
+    MgCapArgs    cap;
 };
 
 // Camera render (mg_render.hip). One device record per camera; a camera's

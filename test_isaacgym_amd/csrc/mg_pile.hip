@@ -492,7 +492,22 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
                     nap += lk >> 16;
                     npt += lk & 0xFFFF;
                 }
-                if (__any(over)) { stop = true; break; }
+                const unsigned long long ob = __ballot(over);
+                if (ob) {
+                    // the list ends here: the refused pair is the
+                    // first lane over; which of the two totals it would have passed
+                    const int lo = __ffsll(ob) - 1;
+                    const int rp = __builtin_amdgcn_readlane(ip, lo), rt = __builtin_amdgcn_readlane(it, lo);
+                    if (ln == 0) {
+                        mg_cap_add(A.cap, MG_CAP_PILE_OVERFLOW, 1);
+                        if (rp > MAXAP) mg_cap_add(A.cap, MG_CAP_PILE_OVER_PAIRS, 1);
+                        if (rt > MAXPT) mg_cap_add(A.cap, MG_CAP_PILE_OVER_POINTS, 1);
+                        atomicOr(A.cap.flags + blockIdx.x,
+                                 (rp > MAXAP ? MG_CAPF_PILE_PAIRS : 0) | (rt > MAXPT ? MG_CAPF_PILE_POINTS : 0));
+                    }
+                    stop = true;
+                    break;
+                }
             }
         }
         __syncthreads();
@@ -561,6 +576,21 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
             }
             ncol = max(ncol, wave_max(Hu.color + 1));
             nrnd = max(nrnd, wave_max(Hu.rnd + 1));
+        }
+        // pairs no sweep will solve: visited with all 64 colours
+        // taken; never visited, the sub-round loop having left by its bound
+        const unsigned long long nc0 = __ballot(ln < nap && H[0].color < 0);
+        const unsigned long long nc1 = __ballot(ln + 64 < nap && H[1].color < 0);
+        if (nc0 | nc1) {
+            const int nounv = __popcll(__ballot(ln < nap && H[0].rnd < 0)) +
+                              __popcll(__ballot(ln + 64 < nap && H[1].rnd < 0));
+            const int nocol = __popcll(nc0) + __popcll(nc1) - nounv;
+            if (ln == 0) {
+                if (nocol) mg_cap_add(A.cap, MG_CAP_PILE_UNCOLOURED, nocol);
+                if (nounv) mg_cap_add(A.cap, MG_CAP_PILE_UNVISITED, nounv);
+                atomicOr(A.cap.flags + blockIdx.x,
+                         (nocol ? MG_CAPF_PILE_COLOURS : 0) | (nounv ? MG_CAPF_PILE_UNVISITED : 0));
+            }
         }
         PSTAMP(6);
         PSTAMP(7);

@@ -347,8 +347,9 @@ __device__ __forceinline__ void shape_candidates(const B& G, const MgStep& P, co
 // the plain build. CREP: the reporting build, stepped while
 // contact reporting is on: the last substep's slots go to the body's staging
 // record, with the impulses that enter fsum.
+// unit: the body's index in the launch (its flag word of the capacity report).
 template <int MAXC, bool MULTI, bool ATTR, bool CREP, class B>
-__device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const MgRigidArgs& A, int b) {
+__device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const MgRigidArgs& A, int b, int unit) {
     constexpr bool CACHE = !MULTI;
     const int nb = A.nb;
     float* S = A.state;
@@ -436,10 +437,13 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
                                  });
             } else {
                 // several shapes: shift-register insert, newest candidate in slot 0
-                int nc = 0;
+                // (ncand counts every candidate, without a branch: those past the
+                // MAXC slots are ignored)
+                int nc = 0, ncand = 0;
                 for (int s = sh0; s < sh0 + nsh; ++s) {
                     shape_candidates(G, P, A.shapes + s * MG_SHAPE_STRIDE, q, x, A.hulls,
                                      [&](int, V3 p, float sep, float mu, float e) {
+                                         ncand += sep < P.contact_offset ? 1 : 0;
                                          if (sep < P.contact_offset && nc < MAXC) {
 #pragma unroll
                                              for (int j = MAXC - 1; j > 0; --j) {
@@ -452,6 +456,16 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
                                              nc = nc + 1;
                                          }
                                      });
+                }
+                // one atomic per counter for the wave, each such body its own flag word
+                const unsigned long long ob = __ballot(ncand > MAXC);
+                if (ob) {
+                    const int ndrop = mg_cap_wave_sum(ncand > MAXC ? ncand - MAXC : 0);
+                    if (ncand > MAXC) atomicOr(A.cap.flags + unit, MG_CAPF_RIGID_SLOTS);
+                    if (threadIdx.x == (unsigned)(__ffsll(ob) - 1)) {
+                        mg_cap_add(A.cap, MG_CAP_RIGID_OVERFLOW, __popcll(ob));
+                        mg_cap_add(A.cap, MG_CAP_RIGID_CANDIDATES_DROPPED, ndrop);
+                    }
                 }
             }
         }
@@ -1486,13 +1500,13 @@ __global__ void __launch_bounds__(64) k_rigid_step(MgStep P, MgRigidArgs A) {
     if (i >= A.nf) return;
     const int b = A.free_ids ? A.free_ids[i] : i;
     if constexpr (UPZ) {
-        rigid_body<MAXC, MULTI, ATTR, CREP>(BasisZ{}, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR, CREP>(BasisZ{}, P, A, b, i);
     } else {
         BasisGen G;
         G.n = v3(P.n[0], P.n[1], P.n[2]);
         G.t1 = v3(P.t1[0], P.t1[1], P.t1[2]);
         G.t2 = v3(P.t2[0], P.t2[1], P.t2[2]);
-        rigid_body<MAXC, MULTI, ATTR, CREP>(G, P, A, b);
+        rigid_body<MAXC, MULTI, ATTR, CREP>(G, P, A, b, i);
     }
 }
 

@@ -191,7 +191,18 @@ struct ModelBufs {
     DevBuf<int> d_pile_body;   // their free bodies' internal slots
     DevBuf<unsigned> d_pile_pairs;  // packed candidate pairs (local shape slots, mg_internal.h)
     DevBuf<int> d_pile_slots;  // [..][2] local shape slots: participant, shape
+    // contact capacity report: the counters, and one flag word
+    // per counted unit: the pile envs, then the coupled envs (rows of d_env),
+    // then the multi-shape free bodies (slots nf1..nf_rigid-1)
+    DevBuf<unsigned long long> d_cap;   // [MG_CAP_N]
+    DevBuf<int> d_cap_flags;            // [n_pile + n_coupled + nf_rigid - nf1]
 };
+
+// the capacity report's counted units (ModelBufs::d_cap_flags): first unit of
+// the coupled envs, of the multi-shape free bodies, and their total
+inline int cap_env0(const MgLayout& L) { return L.n_pile; }
+inline int cap_rigid0(const MgLayout& L) { return L.n_pile + L.n_coupled; }
+inline int cap_units(const MgLayout& L) { return L.n_pile + L.n_coupled + (L.nf_rigid - L.nf1); }
 
 // What mg_upload_model builds apart and commits to the sim as one: the plan
 // (mg_layout.h: counts, storage order, index tables and the host mirrors later
@@ -861,6 +872,8 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
         HIP_TRY(M.d_pile_pairs.upload(L.pile_pairs));
         HIP_TRY(M.d_pile_slots.upload(L.pile_slots, 2));
     }
+    HIP_TRY(M.d_cap.zero(MG_CAP_N));
+    HIP_TRY(M.d_cap_flags.zero((size_t)cap_units(L)));
     HIP_TRY(hipDeviceSynchronize());
     // ---- commit (nothing below fails); the initial state went to the device
     std::vector<float>().swap(L.state0);
@@ -1009,6 +1022,7 @@ static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g) {
     // the contact-moment builds
     if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) A.ctorque = s->d_ctorque;
     A.dof_frc = dof_frc_rows(s, A.crep || A.ctorque || A.jfr);
+    A.cap = {s->d_cap, s->d_cap_flags + cap_env0(s->layout) + g.offset};
     return A;
 }
 
@@ -1025,6 +1039,7 @@ static MgPileArgs pile_args(const mg_sim* s) {
         A.crep_n = s->d_crep_pile_n;
         A.crep_body = s->d_slot_global;
     }
+    A.cap = {s->d_cap, s->d_cap_flags};
     return A;
 }
 
@@ -1057,6 +1072,7 @@ static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
     }
     A.out_rb = O.rb; A.out_root = O.root;
     A.out_body = O.out_body; A.out_root_row = O.out_root_row;
+    A.cap = {s->d_cap, s->d_cap_flags + cap_rigid0(s->layout)};
     return A;
 }
 
@@ -1502,6 +1518,54 @@ int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
     out[0] = s->jfr_ndof;
     out[1] = s->jfr_lanes;
     out[2] = s->jfr_envs;
+    return MG_OK;
+}
+
+// ---- contact capacity report
+int32_t mg_capacity_tracked(mg_sim* s) { return s && s->uploaded && cap_units(s->layout) > 0 ? 1 : 0; }
+
+// the two reads' common opening: the sim's device, nothing while `st` is captured, then the wait
+static int capacity_read_begin(mg_sim* s, hipStream_t st) {
+    if (!s) return fail(MG_ERR_ARG, "null sim");
+    if (!s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    HIP_TRY(hipSetDevice(s->device));
+    if (capture_id(st)) return fail(MG_ERR_STATE, "the capacity report cannot be read while the stream is being captured");
+    HIP_TRY(hipStreamSynchronize(st));
+    return MG_OK;
+}
+
+int32_t mg_capacity_stats(mg_sim* s, int64_t out[MG_CAP_N], int32_t reset, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc_ = capacity_read_begin(s, st)) return rc_;
+    if (!out) return fail(MG_ERR_ARG, "null output");
+    unsigned long long h[MG_CAP_N];
+    HIP_TRY(hipMemcpy(h, s->d_cap, sizeof h, hipMemcpyDeviceToHost));
+    for (int k = 0; k < MG_CAP_N; ++k) out[k] = (int64_t)h[k];
+    if (reset) {
+        HIP_TRY(hipMemsetAsync(s->d_cap, 0, sizeof h, st));
+        const int nu = cap_units(s->layout);
+        if (nu > 0) HIP_TRY(hipMemsetAsync(s->d_cap_flags, 0, (size_t)nu * sizeof(int), st));
+    }
+    return MG_OK;
+}
+
+int32_t mg_capacity_env_flags(mg_sim* s, int32_t* dst_host, int32_t n_envs, void* stream) {
+    if (int rc_ = capacity_read_begin(s, (hipStream_t)stream)) return rc_;
+    const MgLayout& L = s->layout;
+    if (!dst_host) return fail(MG_ERR_ARG, "null destination");
+    if (n_envs != L.nenv) return fail(MG_ERR_ARG, "n_envs is %d, the model has %d envs", n_envs, L.nenv);
+    std::fill(dst_host, dst_host + n_envs, 0);
+    const int nu = cap_units(L);
+    if (nu == 0) return MG_OK;
+    std::vector<int> f((size_t)nu);
+    HIP_TRY(hipMemcpy(f.data(), s->d_cap_flags, (size_t)nu * sizeof(int), hipMemcpyDeviceToHost));
+    // unit -> env from the plan's mirrors
+    auto put = [&](int env, int v) {
+        if (v && env >= 0 && env < n_envs) dst_host[env] |= v;
+    };
+    for (int k = 0; k < L.n_pile; ++k) put(L.pile_env[k], f[k]);
+    for (size_t k = 0; k < L.cenv_row.size(); ++k) put(L.cenv_env[k], f[cap_env0(L) + L.cenv_row[k]]);
+    for (int i = 0; i < L.nf_rigid - L.nf1; ++i) put(L.slot_env[L.nf1 + i], f[cap_rigid0(L) + i]);
     return MG_OK;
 }
 

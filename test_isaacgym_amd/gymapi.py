@@ -253,6 +253,8 @@ class Gym:
                 sim.host_staged = sim.host_stage_parts
             else:
                 N.check(N.lib.mg_fetch_results(sim.native, 1 if wait else 0), "mg_fetch_results")
+            if wait:
+                sim.capacity_autocheck()   # contacts dropped at a kernel's capacity: one stderr line per kind
         return True
 
     def get_sim_time(self, sim):
@@ -1486,6 +1488,21 @@ class Gym:
 
     def get_rigid_contact_reporting(self, sim):
         return bool(sim.contact_reporting[0])
+
+    # ---- contact capacity report (include/migym.h)
+    def get_contact_capacity_report(self, sim, reset=False):
+        """migym extension (PhysX's "contact buffer overflow" message, as
+        numbers): what the step kernels dropped at their fixed capacities since
+        the upload or the last reset. A dict of the counters by name
+        (_native.CAPACITY_COUNTERS: PILE_OVERFLOW ... RIGID_CANDIDATES_DROPPED)
+        and "envs": {env index: [flag names]} (_native.CAPACITY_FLAGS) of every
+        env that dropped something. All zero and no env: the physics ran within
+        every table. Waits for the stream; reset=True zeroes counters and flags
+        after the read. fetch_results(sim, True) looks at the same counters when
+        the frame count is a power of two and names each kind of drop on stderr
+        once (MIGYM_CAPACITY_CHECK=0 in the environment at create_sim: never).
+        Raises MigymError without a device, or while the stream is captured."""
+        return sim.capacity_report(reset)
 
     def _rigid_contacts(self, sim, env=None):
         out = np.zeros(0, dtype=_T.RigidContact.dtype)
