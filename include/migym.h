@@ -701,6 +701,12 @@ int32_t     mg_num_articulations(mg_sim* sim);
 #define MG_RIGID_FORM_REC  2
 #define MG_RIGID_FORM_BOX  4
 int32_t     mg_last_rigid_form(mg_sim* sim);
+/* Diagnostics: out[i] = 1.0f / d[i] for n floats of device memory (both device
+ * pointers, on the current device), computed two at a time by the paired
+ * reciprocal the one-round free-body step forms its rows' effective masses
+ * with (csrc/mg_pair.h rcp2_ieee): IEEE-correct for every float, which the
+ * test of this entry checks. Synchronises the device. < 0 on error. */
+int32_t     mg_debug_rcp_pairs(const float* d, float* out, int32_t n);
 /* Number of envs stepped by the coupled per-env kernel (envs whose bodies can
  * touch each other under the actor_coll rule, e.g. the Franka cube-pick scene,
  * and every env holding a floating-base articulation). */

@@ -205,6 +205,7 @@ def _load():
         "mg_step_time_stats": (i32, [vp, i32, vp, vp, vp]),
         "mg_num_free_bodies": (i32, [vp]),
         "mg_last_rigid_form": (i32, [vp]),
+        "mg_debug_rcp_pairs": (i32, [vp, vp, i32]),
         "mg_num_articulations": (i32, [vp]),
         "mg_num_coupled_envs": (i32, [vp]),
         "mg_num_pile_envs": (i32, [vp]),
@@ -272,7 +273,7 @@ EXPORTED_SYMBOLS = (
     "mg_joint_friction_stats",
     "mg_capacity_stats", "mg_capacity_env_flags", "mg_capacity_tracked",
     "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
-    "mg_last_rigid_form",
+    "mg_last_rigid_form", "mg_debug_rcp_pairs",
 )
 
 

@@ -503,6 +503,8 @@ extern "C" int mg_env_ctab_floats(void);
 int mg_env_ctab_record_floats(int wide);   // one env's contact table in a 16- / 64-lane group
 // form (optional): the MG_RIGID_FORM_* bits of the single-shape launch, -1 when there was none
 hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s, int* form = nullptr);
+// rcp2_ieee (mg_pair.h) over n floats of device memory (mg_debug_rcp_pairs)
+hipError_t mg_launch_rcp_pairs(const float* d, float* out, int n, hipStream_t s);
 hipError_t mg_launch_artic_step(const MgStep& P, const MgArticArgs& A, hipStream_t s);
 hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s);
 hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStream_t s);

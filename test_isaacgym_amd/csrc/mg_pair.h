@@ -19,6 +19,34 @@ MG_HD f2 pk2(float a, float b) { return f2{a, b}; }
 MG_HD f2 bc2(float a) { return f2{a, a}; }
 MG_HD f2 pfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
+#ifdef __HIP__
+// (1.0f / d.x, 1.0f / d.y): the compiler's own expansion of an IEEE f32
+// division (v_div_scale of denominator and numerator, v_rcp, six refinement
+// steps, v_div_fmas, v_div_fixup; denormals stay enabled, no mode switch), with
+// the six steps of the two quotients issued as packed operations. Scaling,
+// reciprocal, the final fmas (each half with its own scale flag) and the fixup
+// stay per half, so each half is the scalar sequence's value for every float
+// (tests/test_rcp_pairs_gpu.py). Device code only (a plain C++ host build of
+// this header, tests/pair_math_check.cpp, does not see it).
+__device__ __forceinline__ f2 rcp2_ieee(f2 d) {
+    bool fx, fy, unused;
+    const float dsx = __builtin_amdgcn_div_scalef(1.0f, d.x, false, &unused);
+    const float dsy = __builtin_amdgcn_div_scalef(1.0f, d.y, false, &unused);
+    const f2 ns = pk2(__builtin_amdgcn_div_scalef(1.0f, d.x, true, &fx),
+                      __builtin_amdgcn_div_scalef(1.0f, d.y, true, &fy));
+    const f2 nd = -pk2(dsx, dsy);
+    const f2 r0 = pk2(__builtin_amdgcn_rcpf(dsx), __builtin_amdgcn_rcpf(dsy));
+    const f2 e0 = pfma(nd, r0, bc2(1.0f));
+    const f2 r1 = pfma(e0, r0, r0);
+    const f2 q0 = ns * r1;
+    const f2 e1 = pfma(nd, q0, ns);
+    const f2 q1 = pfma(e1, r1, q0);
+    const f2 e2 = pfma(nd, q1, ns);
+    return pk2(__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.x, r1.x, q1.x, fx), d.x, 1.0f),
+               __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.y, r1.y, q1.y, fy), d.y, 1.0f));
+}
+#endif
+
 struct V3x2 { f2 x, y, z; };            // (a, b): .x = (a.x, b.x) ...
 struct Q4x2 { f2 x, y, z, w; };
 

@@ -562,6 +562,17 @@ __device__ __forceinline__ void rigid_body(const B& G, const MgStep& P, const Mg
 #ifndef MG_RIGID1_PACK_GEOM
 #define MG_RIGID1_PACK_GEOM 1
 #endif
+// The one-round +Z builds with packed geometry (tgs_zp and the packed row
+// constants), each 0 for the form before it (A/B runs as above):
+// SWEEP_PAIRS: tgs_zp's loops run two sweeps per trip (no impulse copies);
+// RECIP_PAIRS: the rows' effective masses by rcp2_ieee (mg_pair.h) on every
+// lane with one select each, in place of a division per exec bracket.
+#ifndef MG_RIGID1_SWEEP_PAIRS
+#define MG_RIGID1_SWEEP_PAIRS 1
+#endif
+#ifndef MG_RIGID1_RECIP_PAIRS
+#define MG_RIGID1_RECIP_PAIRS 1
+#endif
 // Friction is PhysX's patch friction, as in the coupled
 // step (§3.6.1): the body-ground pair's contacts form one patch whose friction
 // acts at up to two anchors, each fixed on the body (body frame) and on the
@@ -757,6 +768,8 @@ __device__ __forceinline__ void row_normal1(const B& G, NRow& c, V3& v, V3& w, f
 // (f2, pk2, bc2, pfma: mg_pair.h)
 
 // lim1 = share * mu: an anchor row's bound per unit of the patch's normal impulse
+// PAIRS (rigid_body1's PKG builds, MG_RIGID1_SWEEP_PAIRS): two sweeps per loop trip
+template <bool PAIRS>
 __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an)[2], float lim1, float e, V3& v,
                                        V3& w, V3& dx, V3& dth, float invm, bool& c01, bool& c02, bool& c11,
                                        bool& c12) {
@@ -822,36 +835,91 @@ __device__ __forceinline__ void tgs_zp(const MgStep& P, NRow (&sl)[4], ARow (&an
     };
     const f2 nsub = bc2(-P.inv_sub), psub = bc2(P.sub);
     const int nit = P.npos + P.nvel;
-    // sweep order (round 6, as the oracle): a position sweep is the anchors'
-    // rows then the normal rows (non-penetration has the last word before the
-    // velocity is integrated); only the first opens with the normal rows
-    for (int it = 0; it < P.npos; ++it) {
-        const f2 t0 = sep(0) * nsub, t1 = sep(1) * nsub;   // -s / sub of each slot
-        const float tg[4] = {fminf(t0.x, P.max_depen), fminf(t0.y, P.max_depen), fminf(t1.x, P.max_depen),
-                             fminf(t1.y, P.max_depen)};
-        if (it == 0) {
+    if constexpr (PAIRS) {
+        // sweep order (round 6, as the oracle): a position sweep is the anchors'
+        // rows then the normal rows (non-penetration has the last word before the
+        // velocity is integrated); only the first opens with the normal rows.
+        // The first sweep stands in front of the loop, the rest run two per trip
+        // and an odd one after it: a row's new impulse is formed from the old one
+        // and both are read once more (dl = nl - ln), so a loop of one sweep per
+        // trip copied all eight accumulated impulses at its head; with two sweeps
+        // per trip the second writes the registers the first read.
+        auto pos_sweep = [&](bool first, bool last) {
+            const f2 t0 = sep(0) * nsub, t1 = sep(1) * nsub;   // -s / sub of each slot
+            const float tg[4] = {fminf(t0.x, P.max_depen), fminf(t0.y, P.max_depen), fminf(t1.x, P.max_depen),
+                                 fminf(t1.y, P.max_depen)};
+            if (first) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+            }
+            anchors(true, last);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) normal(j, tg[j]);   // same targets: dx, dth unchanged
+            DV = pfma(V, psub, DV);
+            DW = pfma(W, psub, DW);
+            DZ = pfma(Z, psub, DZ);
+        };
+        auto vel_sweep = [&](const float (&tg)[4], bool last) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+            anchors(false, last);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+        };
+        if (P.npos > 0) {
+            pos_sweep(true, nit == 1);
+            int it = 1;
+            for (; it + 2 <= P.npos; it += 2) {
+                pos_sweep(false, false);   // a sweep followed by another is never the last
+                pos_sweep(false, it + 1 == nit - 1);
+            }
+            if (it < P.npos) pos_sweep(false, it == nit - 1);
         }
-        anchors(true, it == nit - 1);
+        if (P.nvel > 0) {
+            const f2 s01 = sep(0), s23 = sep(1);
+            const float sj[4] = {s01.x, s01.y, s23.x, s23.y};
+            float tg[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) normal(j, tg[j]);   // same targets: dx, dth unchanged
-        DV = pfma(V, psub, DV);
-        DW = pfma(W, psub, DW);
-        DZ = pfma(Z, psub, DZ);
-    }
-    if (P.nvel > 0) {
-        const f2 s01 = sep(0), s23 = sep(1);
-        const float sj[4] = {s01.x, s01.y, s23.x, s23.y};
-        float tg[4];
+            for (int j = 0; j < 4; ++j) tg[j] = vel_target(P, sj[j], e, sl[j].vn0);
+            int it = P.npos;
+            for (; it + 2 <= nit; it += 2) {
+                vel_sweep(tg, false);
+                vel_sweep(tg, it + 1 == nit - 1);
+            }
+            if (it < nit) vel_sweep(tg, true);
+        }
+    } else {
+        // sweep order (round 6, as the oracle): a position sweep is the anchors'
+        // rows then the normal rows (non-penetration has the last word before the
+        // velocity is integrated); only the first opens with the normal rows
+        for (int it = 0; it < P.npos; ++it) {
+            const f2 t0 = sep(0) * nsub, t1 = sep(1) * nsub;   // -s / sub of each slot
+            const float tg[4] = {fminf(t0.x, P.max_depen), fminf(t0.y, P.max_depen), fminf(t1.x, P.max_depen),
+                                 fminf(t1.y, P.max_depen)};
+            if (it == 0) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tg[j] = vel_target(P, sj[j], e, sl[j].vn0);
-        for (int it = P.npos; it < nit; ++it) {
+                for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+            }
+            anchors(true, it == nit - 1);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) normal(j, tg[j]);
-            anchors(false, it == nit - 1);
+            for (int j = 0; j < 4; ++j) normal(j, tg[j]);   // same targets: dx, dth unchanged
+            DV = pfma(V, psub, DV);
+            DW = pfma(W, psub, DW);
+            DZ = pfma(Z, psub, DZ);
+        }
+        if (P.nvel > 0) {
+            const f2 s01 = sep(0), s23 = sep(1);
+            const float sj[4] = {s01.x, s01.y, s23.x, s23.y};
+            float tg[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+            for (int j = 0; j < 4; ++j) tg[j] = vel_target(P, sj[j], e, sl[j].vn0);
+            for (int it = P.npos; it < nit; ++it) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+                anchors(false, it == nit - 1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) normal(j, tg[j]);
+            }
         }
     }
     v = v3(V.x, V.y, Z.y);
@@ -1035,8 +1103,20 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
                 for (int j = 0; j < 4; ++j) {
                     const f2 Ixy = z_iwn_xy(Ip, sl[j].r);
                     sl[j].In = v3(Ixy.x, Ixy.y, z_iwn_z(Iw, sl[j].r));
-                    sl[j].kn = on[j] ? 1.0f / (invm + G.kn(sl[j].r, sl[j].In)) : 0.0f;
+                    if constexpr (!MG_RIGID1_RECIP_PAIRS)
+                        sl[j].kn = on[j] ? 1.0f / (invm + G.kn(sl[j].r, sl[j].In)) : 0.0f;
                     sl[j].ln = 0.0f;
+                }
+                if constexpr (MG_RIGID1_RECIP_PAIRS) {
+                    // two slots' denominators as one pair, both reciprocals on
+                    // every lane (an inactive slot has r = 0: 1 / invm, unused)
+#pragma unroll
+                    for (int j = 0; j < 4; j += 2) {
+                        const f2 kn = rcp2_ieee(bc2(invm) + z_kn2(v3x2(sl[j].r, sl[j + 1].r),
+                                                                   v3x2(sl[j].In, sl[j + 1].In)));
+                        sl[j].kn = on[j] ? kn.x : 0.0f;
+                        sl[j + 1].kn = on[j + 1] ? kn.y : 0.0f;
+                    }
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j += 2) {
@@ -1057,8 +1137,16 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
                     an[a].r = r;
                     an[a].I1 = v3(I1xy.x, I1xy.y, z_iw1_z(Iw, r));
                     an[a].I2 = v3(I2xy.x, I2xy.y, z_iw2_z(Iw, r));
-                    an[a].k1 = act ? 1.0f / (invm + G.k1(r, an[a].I1)) : 0.0f;
-                    an[a].k2 = act ? 1.0f / (invm + G.k2(r, an[a].I2)) : 0.0f;
+                    if constexpr (MG_RIGID1_RECIP_PAIRS) {
+                        // (k1, k2): z_k1 and z_k2 (mg_pair.h) term by term as one pair
+                        const f2 k = rcp2_ieee(bc2(invm) + (bc2(-r.z) * pk2(an[a].I1.x, an[a].I2.y) +
+                                                            pk2(r.x, r.y) * pk2(an[a].I1.z, an[a].I2.z)));
+                        an[a].k1 = act ? k.x : 0.0f;
+                        an[a].k2 = act ? k.y : 0.0f;
+                    } else {
+                        an[a].k1 = act ? 1.0f / (invm + G.k1(r, an[a].I1)) : 0.0f;
+                        an[a].k2 = act ? 1.0f / (invm + G.k2(r, an[a].I2)) : 0.0f;
+                    }
                     an[a].l1 = 0.0f;
                     an[a].l2 = 0.0f;
                     an[a].e1 = act ? fminf(fmaxf(a ? E1.y : E1.x, -P.max_depen), P.max_depen) : 0.0f;
@@ -1110,7 +1198,7 @@ __device__ __forceinline__ int rigid_body1(const B& G, const MgStep& P, const fl
             RUSE(an[1].k2); RUSE(sl[3].kn);
             if (st < 2) RSTAMP(6 + 6 * st);   // row constants, anchor rows
             if constexpr (B::kPacked && PACK) {
-                tgs_zp(P, sl, an, share * mu, e, v, w, dx, dth, invm, c01, c02, c11, c12);
+                tgs_zp<PKG && MG_RIGID1_SWEEP_PAIRS>(P, sl, an, share * mu, e, v, w, dx, dth, invm, c01, c02, c11, c12);
             } else
             for (int it = 0; it < nit; ++it) {
                 const bool pos = it < P.npos, last = it == nit - 1;
@@ -1510,7 +1598,25 @@ __global__ void __launch_bounds__(64) k_rigid_step(MgStep P, MgRigidArgs A) {
     }
 }
 
+// rcp2_ieee (mg_pair.h) over an array, a pair per lane; an odd count's last
+// pair takes 1 for its missing half (tests/test_rcp_pairs_gpu.py)
+__global__ void __launch_bounds__(256) k_rcp_pairs(const float* d, float* out, int n) {
+    const int i = 2 * (blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const bool two = i + 1 < n;
+    const f2 r = rcp2_ieee(pk2(d[i], two ? d[i + 1] : 1.0f));
+    out[i] = r.x;
+    if (two) out[i + 1] = r.y;
+}
+
 }  // namespace
+
+hipError_t mg_launch_rcp_pairs(const float* d, float* out, int n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const int pairs = (n + 1) / 2;
+    hipLaunchKernelGGL(k_rcp_pairs, dim3((pairs + 255) / 256), dim3(256), 0, s, d, out, n);
+    return hipGetLastError();
+}
 
 bool mg_step_is_upz(const MgStep& P) {
     return P.n[0] == 0.0f && P.n[1] == 0.0f && P.n[2] == 1.0f && P.t1[0] == 0.0f && P.t1[1] == 1.0f &&

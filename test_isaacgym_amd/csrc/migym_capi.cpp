@@ -1716,6 +1716,15 @@ int32_t mg_cube_pick_step(const mg_cube_pick_args* a, void* stream) {
     return MG_OK;
 }
 
+// diagnostics (tests/test_rcp_pairs_gpu.py): the paired reciprocal of the
+// free-body step's row constants over a device array, on the current device
+int32_t mg_debug_rcp_pairs(const float* d, float* out, int32_t n) {
+    if (n < 0 || (n > 0 && (!d || !out))) return fail(MG_ERR_ARG, "bad arguments");
+    HIP_TRY(mg_launch_rcp_pairs(d, out, n, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    return MG_OK;
+}
+
 int32_t mg_last_rigid_form(mg_sim* s) { return s ? s->rigid_form : -1; }
 int32_t mg_num_free_bodies(mg_sim* s) { return s ? s->layout.nf : 0; }
 int32_t mg_num_articulations(mg_sim* s) { return s ? s->layout.nartic : 0; }
