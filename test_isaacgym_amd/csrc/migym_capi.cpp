@@ -18,6 +18,7 @@
 #include "mg_chainlink.h"
 #include "mg_attractor.h"
 #include "mg_layout.h"
+#include "mg_fusion.h"
 
 thread_local MgKernelTimer* mg_timer = nullptr;
 
@@ -250,31 +251,8 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     mg_sim_params params{};
     bool uploaded = false;
 
-    // Step fusion (mg_set_fusion): a device-resident, non-indexed root-state set
-    // of a sim whose actor roots are all single-shape free bodies
-    // (layout.roots_free) is read by the next simulate's free-body kernel
-    // (d_root_row) instead of a scatter launch; any earlier reader of the
-    // state flushes it as the scatter. A root refresh into the bound root tensor
-    // also gathers the bound rigid-body tensor (one launch), and the rigid-body
-    // refresh that follows is served by it while the state is unchanged.
-    int fusion = 0;   // opt-in (mg_set_fusion): Isaac Gym copies at set time and refreshes exactly what is asked
-    const float* pend_root = nullptr;
-    const float* pend_tgt[3] = {nullptr, nullptr, nullptr};   // fused DOF target sets (pos, vel, force)
-    // stream-capture id (0: eager) at which each deferred set / the paired
-    // refresh happened: fused work is only combined within one capture (or
-    // eagerly), so a graph never relies on work it did not record
-    unsigned long long pend_root_cap = 0, pend_tgt_cap[3] = {0, 0, 0}, rb_cap = 0;
-    float* bind_root = nullptr;
-    float* bind_rb = nullptr;
-    float* bind_dof = nullptr;    // the persistent DOF-state tensor (mg_bind_dof_refresh_target)
-    long long state_gen = 0, rb_gen = -1, out_gen = -1;   // out_gen: bound tensors written by the step
-    unsigned long long out_cap = 0;
-    // DOF state generation (simulate, mg_set_dof_state) and the one the step
-    // wrote into the bound DOF tensor (MG_FUSE_STEP_OUT; layout.step_out_ok:
-    // it covers the sim)
-    long long dof_sgen = 0, dof_gen = -1;
-    unsigned long long dof_cap = 0;
-    int last_set_deferred = 0;    // the last mg_set_* left its source to be read by the next simulate
+    MgFusion fuse;    // step fusion (mg_set_fusion): the deferred sets and the fresh copies
+    hipStream_t set_st[4] = {};   // the stream each deferred set was made on: root, target columns (apply_stream)
     bool ext_pending = false;
 
     DevBuf<float> d_stage;     // host-transfer staging (floats)
@@ -283,8 +261,7 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     // step kernel (no scatter launch; h_root_in below); and from the
     // first mg_fetch_host_state on, the step kernels that write their own rows
     // (step_out_ok) write root / rigid-body / DOF rows into d_host_out, laid out as
-    // the host stage, so the fetch copies them without gathering (ho_*_gen: the
-    // state generation they hold)
+    // the host stage, so the fetch copies them without gathering
     // host sources are copied at the set call into this page-locked buffer (then
     // sent in stream order), so the caller may overwrite its tensor right away —
     // Isaac Gym's copy-at-set — even though the transfer itself is asynchronous;
@@ -309,9 +286,6 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     float* d_root_in_alias = nullptr;
     hipEvent_t root_ev = nullptr;
     bool root_ev_pending = false;
-    bool ho_alias = false;            // the last fetch staged into h_stage: the step writes there
-    const float* ho_written = nullptr;   // the stage the last simulate wrote (ho_*_gen refer to it)
-    long long ho_root_gen = -1, ho_rb_gen = -1, ho_dof_gen = -1;
     DevBuf<int> d_stage_idx;
     size_t stage_idx_n = 0;
 
@@ -520,32 +494,44 @@ unsigned long long capture_id(hipStream_t st) {
     if (hipStreamGetCaptureInfo(st, &cs, &id) != hipSuccess || cs != hipStreamCaptureStatusActive) return 0;
     return id + 1;
 }
-// may this call defer / combine work? always eagerly; inside a stream capture
-// only when the caller opted in (MG_FUSE_IN_CAPTURE): a deferred set left at
-// the end of a captured region would never be applied by its replays
-bool fuse_here(const mg_sim* s, unsigned long long cid) { return cid == 0 || (s->fusion & MG_FUSE_IN_CAPTURE); }
 
-// apply a deferred root-state set as the ordinary scatter (a reader of the
-// state comes before the next simulate)
-int flush_root(mg_sim* s, hipStream_t st) {
-    if (!s->pend_root) return MG_OK;
-    const float* src = s->pend_root;
-    s->pend_root = nullptr;
-    HIP_TRY(mg_launch_scatter_rows(src, MG_STATE_N, s->d_actor_root, nullptr, s->layout.na, s->layout.na, s->d_state, s->layout.nb, st));
-    if (src == s->d_root_in_alias) {   // the mapped input buffer's reader
-        HIP_TRY(hipEventRecord(s->root_ev, st));
-        s->root_ev_pending = true;
-    }
+// `st` now reads the mapped root input buffer, if that is what `src` is
+int root_in_read(mg_sim* s, const float* src, hipStream_t st) {
+    if (!src || src != s->d_root_in_alias) return MG_OK;
+    HIP_TRY(hipEventRecord(s->root_ev, st));
+    s->root_ev_pending = true;
     return MG_OK;
 }
 
-// apply a deferred DOF target column (0 pos, 1 vel, 2 force) as a copy
-int flush_tgt(mg_sim* s, int k, hipStream_t st) {
-    if (!s->pend_tgt[k]) return MG_OK;
-    const float* src = s->pend_tgt[k];
-    s->pend_tgt[k] = nullptr;
-    HIP_TRY(hipMemcpyAsync(s->d_dof_tgt + (size_t)k * s->layout.nd, src, (size_t)s->layout.nd * sizeof(float),
-                           hipMemcpyDeviceToDevice, st));
+// Where a deferred set the ledger hands back is launched: on the caller's
+// stream; one made eagerly and handed back inside a capture (a.outside) on the
+// stream it was made on (set_st: root, target columns), where it lands once, as
+// it did at the set call without fusion. Recorded into the graph, every replay
+// would apply it again. (Made on the capturing stream itself, it can only be recorded.)
+hipStream_t apply_stream(const mg_sim* s, int which, const MgFusion::Apply& a, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (!a.outside || hipStreamIsCapturing(s->set_st[which], &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+        return st;
+    return s->set_st[which];
+}
+
+// apply a root-state set the ledger had deferred (null: none) as the ordinary scatter
+int apply_root(mg_sim* s, const MgFusion::Apply& a, hipStream_t st) {
+    if (!a.src) return MG_OK;
+    st = apply_stream(s, 0, a, st);
+    HIP_TRY(mg_launch_scatter_rows(a.src, MG_STATE_N, s->d_actor_root, nullptr, s->layout.na, s->layout.na, s->d_state, s->layout.nb, st));
+    return root_in_read(s, a.src, st);
+}
+// what every reader of d_state opens with
+int flush_root(mg_sim* s, hipStream_t st) {
+    return s->fuse.root_pending() ? apply_root(s, s->fuse.read_state(capture_id(st)), st) : MG_OK;
+}
+
+// apply a deferred DOF target column (0 pos, 1 vel, 2 force; null: none) as a copy
+int apply_tgt(mg_sim* s, int k, const MgFusion::Apply& a, hipStream_t st) {
+    if (!a.src) return MG_OK;
+    HIP_TRY(hipMemcpyAsync(s->d_dof_tgt + (size_t)k * s->layout.nd, a.src, (size_t)s->layout.nd * sizeof(float),
+                           hipMemcpyDeviceToDevice, apply_stream(s, 1 + k, a, st)));
     return MG_OK;
 }
 
@@ -884,15 +870,15 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     return MG_OK;
 }
 
-// the pending DOF target columns as the kernels' inputs, with write-through
-static void fused_targets(mg_sim* s, const float*& tp, const float*& tv, const float*& tf, float*& wp, float*& wv,
-                          float*& wf) {
+// the deferred DOF target columns as the kernels' inputs, with write-through
+static void fused_targets(const mg_sim* s, const MgFusion::Step& fs, const float*& tp, const float*& tv, const float*& tf,
+                          float*& wp, float*& wv, float*& wf) {
     const float** in[3] = {&tp, &tv, &tf};
     float** out[3] = {&wp, &wv, &wf};
     for (int k = 0; k < 3; ++k) {
         *out[k] = nullptr;
-        if (s->pend_tgt[k]) {
-            *in[k] = s->pend_tgt[k];
+        if (fs.tgt[k]) {
+            *in[k] = fs.tgt[k];
             *out[k] = s->d_dof_tgt + (size_t)k * s->layout.nd;
         }
     }
@@ -921,10 +907,25 @@ static bool step_writes_rows(const mg_sim* s) {
 
 // Where the step kernels write the refreshed rows themselves: the bound tensors
 // (MG_FUSE_STEP_OUT) or the host stage (mg_fetch_host_state), each optional; all null: nowhere.
+// With them the ledger's answer itself (fs): the deferred sets these kernels read.
 struct StepOut {
     float *rb = nullptr, *root = nullptr, *dof = nullptr;
     const int *out_body = nullptr, *out_root_row = nullptr;   // internal slot -> global body / actor row (or -1)
+    MgFusion::Step fs{};
 };
+static StepOut step_out(const mg_sim* s, const MgFusion::Step& fs) {
+    StepOut O;
+    O.fs = fs;
+    if (fs.out == MG_OUT_NONE) return O;
+    O.out_body = s->d_slot_global;
+    O.out_root_row = s->d_slot_actor;
+    O.root = fs.root; O.rb = fs.rb; O.dof = fs.dof;
+    if (fs.out == MG_OUT_STAGE) {   // the host stage's layout (mg_fetch_host_state)
+        O.rb = fs.root + (size_t)s->layout.na * MG_STATE_N;
+        O.dof = s->layout.nd ? fs.root + (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N : nullptr;
+    }
+    return O;
+}
 
 // The DOF force rows of a launch, or null: written while the sim reports DOF forces, and by every
 // contact-moment, reporting and joint-friction build (`feature`; the refresh masks the other rows).
@@ -951,7 +952,7 @@ static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
     A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
     A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
     A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
-    fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
+    fused_targets(s, O.fs, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
@@ -981,7 +982,7 @@ static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
 }
 
 // the coupled step of one env group (mg_env.hip)
-static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g) {
+static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g, const MgFusion::Step& fs) {
     MgEnvArgs A{};
     A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
     A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
@@ -1003,7 +1004,7 @@ static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g) {
     A.nshape = s->layout.ns;
     A.dof_pos = s->d_dof; A.dof_vel = s->d_dof + s->layout.nd;
     A.dof_tpos = s->d_dof_tgt; A.dof_tvel = s->d_dof_tgt + s->layout.nd; A.dof_force = s->d_dof_tgt + 2 * (size_t)s->layout.nd;
-    fused_targets(s, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
+    fused_targets(s, fs, A.dof_tpos, A.dof_tvel, A.dof_force, A.tpos_w, A.tvel_w, A.force_w);
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
@@ -1043,7 +1044,7 @@ static MgPileArgs pile_args(const mg_sim* s) {
     return A;
 }
 
-// the free-body step; a deferred root set (s->pend_root) is read by the kernel
+// the free-body step; a deferred root set (O.fs.root_src) is read by the kernel
 static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
     MgRigidArgs A{};
     A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
@@ -1066,8 +1067,8 @@ static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
         A.crep_body = s->d_slot_global;
         A.crep_stride = std::max(s->layout.nf_rigid, 1);
     }
-    if (s->pend_root) {
-        A.root_src = s->pend_root;
+    if (O.fs.root_src) {
+        A.root_src = O.fs.root_src;
         A.root_row = s->d_root_row;
     }
     A.out_rb = O.rb; A.out_root = O.root;
@@ -1103,34 +1104,33 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const MgStep P = make_step(s->params);
     s->rigid_form = -1;   // this simulate's, or none (mg_last_rigid_form)
-    {   // deferred sets of another capture (or of the eager stream while capturing):
-        // applied here as ordinary launches, not read by this step's kernels
-        const unsigned long long cid = capture_id(st);
-        if (s->pend_root && s->pend_root_cap != cid)
-            if (int rc_ = flush_root(s, st)) return rc_;
-        for (int k = 0; k < 3; ++k)
-            if (s->pend_tgt[k] && s->pend_tgt_cap[k] != cid)
-                if (int rc_ = flush_tgt(s, k, st)) return rc_;
-    }
     // Under HIP stream capture (a hipGraph of the tensor-API step) the launches
     // are recorded as graph nodes; the timing events are left out (they would
     // become fixed nodes of the graph) and fetch_results does not block.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(st, &cap));
     s->capturing = cap != hipStreamCaptureStatusNone;
+    // ---- refusals. Rigid-body attractors, sensors, joint friction: a table
+    // this build cannot honour is refused, never ignored
+    if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
+    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
+    if (s->jfr_ndof > 0)
+        if (int rc_ = jfr_refusal(s)) return rc_;
+    if (s->attr_dirty && s->capturing)
+        return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
+    // ---- begin: deferred sets this step's kernels do not read are applied as ordinary launches
+    const unsigned long long cid = capture_id(st);
+    const MgFusion::Begin fb =
+        s->fuse.begin_simulate(cid, s->layout.nf_rigid > 0, !s->groups.empty() || !s->env_groups.empty());
+    if (int rc_ = apply_root(s, fb.root, st)) return rc_;
+    for (int k = 0; k < 3; ++k)
+        if (int rc_ = apply_tgt(s, k, fb.tgt[k], st)) return rc_;
     MgKernelTimer timer{};
     struct TimerScope {
         ~TimerScope() { mg_timer = nullptr; }
     } timer_scope;
     int slot = 0;
-    // rigid-body attractors: a table this build cannot honour is refused, never
-    // ignored; a changed table is sent here, in stream order before the step
-    if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
-    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
-    if (s->jfr_ndof > 0)
-        if (int rc_ = jfr_refusal(s)) return rc_;
-    if (s->attr_dirty) {
-        if (s->capturing) return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
+    if (s->attr_dirty) {   // a changed attractor table is sent here, in stream order before the step
         HIP_TRY(hipMemcpyAsync(s->d_attr, s->h_attr, s->attrs.size() * MG_ATTR_N * sizeof(float),
                                hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(s->attr_ev, st));
@@ -1148,29 +1148,18 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         timer.cap = mg_sim::kKern;
         mg_timer = &timer;
     }
-    // the refresh fused into the step (MG_FUSE_STEP_OUT): every body's rows are
-    // written by the kernel that steps it (s->layout.step_out_ok), into the bound
-    // tensors (each one optional)
     if (s->n_sens > 0) {
         // force sensors: which articulations begin the frame with a state set
         // (a deferred root set is applied first, so that the comparison sees it)
         if (int rc_ = flush_root(s, st)) return rc_;
         HIP_TRY(mg_launch_sensor_mark(sensor_args(s, P), st));
     }
-    const unsigned long long step_cid = capture_id(st);
-    StepOut O;
-    const bool step_out = (s->fusion & MG_FUSE_STEP_OUT) && fuse_here(s, step_cid) && step_writes_rows(s) &&
-                          (s->bind_root || s->bind_rb || s->bind_dof);
-    // the CPU pipeline's output stage (mg_fetch_host_state): the same kernels
-    // write into the library's own buffer, so no caller-visible tensor changes
-    float* ho_base = s->ho_alias ? s->d_stage_alias : s->d_host_out;
-    const bool host_out = !step_out && ho_base && step_writes_rows(s) && step_cid == 0;
-    if (step_out)
-        O = {s->bind_rb, s->bind_root, s->bind_dof, s->d_slot_global, s->d_slot_actor};
-    else if (host_out)
-        O = {ho_base + (size_t)s->layout.na * MG_STATE_N, ho_base,
-             s->layout.nd ? ho_base + (size_t)(s->layout.na + s->layout.nb) * MG_STATE_N : nullptr, s->d_slot_global,
-             s->d_slot_actor};
+    // ---- the launches. The kernels read the deferred sets of this capture, and
+    // write the refreshed rows themselves where the ledger says: into the bound
+    // tensors (MG_FUSE_STEP_OUT), else into the CPU pipeline's output stage
+    // (mg_fetch_host_state: the library's own buffer, so no caller-visible tensor changes)
+    const MgFusion::Step fs = s->fuse.step(cid, step_writes_rows(s));
+    const StepOut O = step_out(s, fs);
     for (size_t gi = 0; gi < s->groups.size(); ++gi) {
         const ArticGroup& g = s->groups[gi];
         if (g.step_count == 0) continue;
@@ -1184,7 +1173,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         }
     }
     for (const EnvGroup& g : s->env_groups) {
-        hipError_t e = mg_launch_env_step(P, env_args(s, g), st);
+        hipError_t e = mg_launch_env_step(P, env_args(s, g, fs), st);
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
     }
     if (s->layout.n_pile > 0) {
@@ -1192,33 +1181,11 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
     }
     if (s->layout.nf_rigid > 0) {
-        const MgRigidArgs A = rigid_args(s, O);
-        const bool reads_root_in = s->pend_root && s->pend_root == s->d_root_in_alias;
-        s->pend_root = nullptr;   // the deferred root set: read by the step kernel
-        HIP_TRY(mg_launch_rigid_step(P, A, st, &s->rigid_form));
-        if (reads_root_in) {
-            HIP_TRY(hipEventRecord(s->root_ev, st));
-            s->root_ev_pending = true;
-        }
+        HIP_TRY(mg_launch_rigid_step(P, rigid_args(s, O), st, &s->rigid_form));
+        if (int rc_ = root_in_read(s, fs.root_src, st)) return rc_;
     }
-    if (int rc_ = flush_root(s, st)) return rc_;   // a root set with no free-body launch
-    if (s->groups.empty() && s->env_groups.empty())
-        for (int k = 0; k < 3; ++k)
-            if (int rc_ = flush_tgt(s, k, st)) return rc_;
-    for (int k = 0; k < 3; ++k) s->pend_tgt[k] = nullptr;   // read (and written through) by the step
-    s->state_gen++;
-    s->dof_sgen++;
-    if (host_out) {
-        s->ho_written = ho_base;
-        s->ho_root_gen = s->state_gen;
-        s->ho_rb_gen = s->state_gen;
-        s->ho_dof_gen = O.dof ? s->dof_sgen : -1;
-    }
-    if (step_out) {
-        if (s->bind_root) { s->out_gen = s->state_gen; s->out_cap = step_cid; }
-        if (s->bind_rb) { s->rb_gen = s->state_gen; s->rb_cap = step_cid; }
-        if (s->bind_dof) { s->dof_gen = s->dof_sgen; s->dof_cap = step_cid; }
-    }
+    // ---- end: the deferred sets were read (and the targets written through), the outputs written
+    s->fuse.end_simulate(fs, cid);
     if (s->crep_on) {
         HIP_TRY(mg_launch_contact_compact(contact_args(s), st));
         s->crep_valid = true;
@@ -1273,26 +1240,23 @@ int32_t mg_fetch_host_state(mg_sim* s, float* dst, int32_t parts, void* stream) 
     const bool alias = s->h_stage && dst == s->h_stage && s->h_stage_n >= off[4];
     if (!alias && s->host_out_n < off[4]) {   // the output stage (simulate writes into it from now on)
         s->host_out_n = 0;
+        s->fuse.stage_freed(s->d_host_out);
         HIP_TRY(s->d_host_out.alloc(off[4]));
         s->host_out_n = off[4];
-        if (s->ho_written && !s->ho_alias) s->ho_written = nullptr;
     }
-    s->ho_alias = alias;
     float* base = alias ? s->d_stage_alias : s->d_host_out;
-    const bool fresh = s->ho_written == base;
+    // parts the last simulate wrote there, with no state change since: no gather
+    const int need = s->fuse.fetch(base) | 8;
     int lo = -1, hi = -1;
     for (int k = 0; k < 4; ++k) {
         if (!((parts >> k) & 1) || off[k + 1] == off[k]) continue;
         if (lo < 0) lo = k;
         hi = k;
         float* d = base + off[k];
-        // parts the last simulate wrote there, with no state change since: no gather
-        if (k == 0 && !(fresh && s->ho_root_gen == s->state_gen))
-            HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_actor_root, s->layout.na, d, st));
-        if (k == 1 && !(fresh && s->ho_rb_gen == s->state_gen))
-            HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, d, st));
-        if (k == 2 && !(fresh && s->ho_dof_gen == s->dof_sgen))
-            HIP_TRY(mg_launch_gather_rows(s->d_dof, s->layout.nd, 2, nullptr, s->layout.nd, d, st));
+        if (!((need >> k) & 1)) continue;
+        if (k == 0) HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_actor_root, s->layout.na, d, st));
+        if (k == 1) HIP_TRY(mg_launch_gather_rows(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, d, st));
+        if (k == 2) HIP_TRY(mg_launch_gather_rows(s->d_dof, s->layout.nd, 2, nullptr, s->layout.nd, d, st));
         if (k == 3) HIP_TRY(mg_launch_gather_rows(s->d_cforce, s->layout.nb, 3, s->d_perm, s->layout.nb, d, st));
     }
     if (lo >= 0 && !alias)
@@ -1458,8 +1422,7 @@ float* mg_host_stage(mg_sim* s, int64_t nfloat) {
         s->h_stage.reset();
         s->d_stage_alias = nullptr;
         s->h_stage_n = 0;
-        s->ho_alias = false;
-        s->ho_written = nullptr;
+        s->fuse.stage_replaced(s->d_host_out);
     }
     HostBuf<float> h;
     if (h.alloc((size_t)nfloat, true) != hipSuccess) {
@@ -1480,37 +1443,28 @@ float* mg_host_stage(mg_sim* s, int64_t nfloat) {
 
 int32_t mg_set_fusion(mg_sim* s, int32_t flags) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    const int32_t prev = s->fusion;
-    s->fusion = flags & (MG_FUSE_ROOT_SET | MG_FUSE_REFRESH | MG_FUSE_DOF_TARGETS | MG_FUSE_IN_CAPTURE | MG_FUSE_STEP_OUT);
-    return prev;
+    return s->fuse.set_flags(flags);
 }
 
 int32_t mg_bind_refresh_targets(mg_sim* s, float* root_dst, float* rigid_body_dst) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    s->bind_root = root_dst;
-    s->bind_rb = rigid_body_dst;
-    s->rb_gen = -1;
-    s->out_gen = -1;
+    s->fuse.bind(root_dst, rigid_body_dst);
     return MG_OK;
 }
 
 int32_t mg_bind_dof_refresh_target(mg_sim* s, float* dof_dst) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    s->bind_dof = dof_dst;
-    s->dof_gen = -1;
+    s->fuse.bind_dof(dof_dst);
     return MG_OK;
 }
 
 int32_t mg_discard_pending_sets(mg_sim* s) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    s->pend_root = nullptr;
-    for (int k = 0; k < 3; ++k) s->pend_tgt[k] = nullptr;
+    s->fuse.discard();
     return MG_OK;
 }
 
-int32_t mg_step_out_supported(mg_sim* s) {
-    return s && s->uploaded && s->layout.step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0 ? 1 : 0;
-}
+int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && step_writes_rows(s) ? 1 : 0; }
 
 int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
@@ -1569,7 +1523,7 @@ int32_t mg_capacity_env_flags(mg_sim* s, int32_t* dst_host, int32_t n_envs, void
     return MG_OK;
 }
 
-int32_t mg_last_set_deferred(mg_sim* s) { return s ? s->last_set_deferred : 0; }
+int32_t mg_last_set_deferred(mg_sim* s) { return s ? s->fuse.last_set_deferred : 0; }
 
 int32_t mg_set_kernel_timing(mg_sim* s, int32_t on) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
@@ -1738,16 +1692,12 @@ int32_t mg_refresh_actor_root_state(mg_sim* s, float* dst, int32_t dst_host, voi
     HIP_TRY(hipSetDevice(s->device));
     if (int rc_ = flush_root(s, st)) return rc_;
     const unsigned long long cid = capture_id(st);
-    if (!dst_host && dst && dst == s->bind_root && (s->fusion & MG_FUSE_STEP_OUT) && s->out_gen == s->state_gen &&
-        s->out_cap == cid)
-        return MG_OK;   // written by the step kernel (MG_FUSE_STEP_OUT)
-    if (!dst_host && dst && dst == s->bind_root && s->bind_rb && (s->fusion & MG_FUSE_REFRESH) &&
-        fuse_here(s, cid) && s->layout.na > 0) {
-        // the bound root and rigid-body tensors in one launch
-        HIP_TRY(mg_launch_gather_rb_root(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, s->bind_rb, s->d_body_actor,
+    const MgFusion::Refresh r = s->fuse.refresh(MG_PART_ROOT, dst, dst_host, cid, s->layout.na > 0);
+    if (r.how == MG_REFRESH_SKIP) return MG_OK;   // written by the step kernel
+    if (r.how == MG_REFRESH_PAIRED) {   // the bound root and rigid-body tensors in one launch
+        HIP_TRY(mg_launch_gather_rb_root(s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, r.rb, s->d_body_actor,
                                          dst, st));
-        s->rb_gen = s->state_gen;
-        s->rb_cap = cid;
+        s->fuse.refreshed(r, cid);
         return MG_OK;
     }
     return refresh_rows(s, s->d_state, s->layout.nb, MG_STATE_N, s->d_actor_root, s->layout.na, dst, dst_host, st);
@@ -1758,22 +1708,18 @@ int32_t mg_refresh_rigid_body_state(mg_sim* s, float* dst, int32_t dst_host, voi
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->device));
     if (int rc_ = flush_root(s, st)) return rc_;
-    const bool bound = !dst_host && dst && dst == s->bind_rb;
-    if (bound && (s->fusion & (MG_FUSE_REFRESH | MG_FUSE_STEP_OUT)) && s->rb_gen == s->state_gen &&
-        s->rb_cap == capture_id(st))
-        return MG_OK;   // served by the paired gather / the step kernel of the same capture (or eagerly)
+    const unsigned long long cid = capture_id(st);
+    const MgFusion::Refresh r = s->fuse.refresh(MG_PART_RB, dst, dst_host, cid, s->layout.na > 0);
+    if (r.how == MG_REFRESH_SKIP) return MG_OK;   // served by the paired gather / the step kernel
     const int rc = refresh_rows(s, s->d_state, s->layout.nb, MG_STATE_N, s->d_perm, s->layout.nb, dst, dst_host, st);
-    if (rc == MG_OK && bound) {
-        s->rb_gen = s->state_gen;
-        s->rb_cap = capture_id(st);
-    }
+    if (rc == MG_OK) s->fuse.refreshed(r, cid);
     return rc;
 }
 int32_t mg_refresh_dof_state(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s) return fail(MG_ERR_ARG, "null sim");
-    if (!dst_host && dst && dst == s->bind_dof && (s->fusion & MG_FUSE_STEP_OUT) && s->dof_gen == s->dof_sgen &&
-        s->dof_cap == capture_id((hipStream_t)stream))
-        return MG_OK;   // written by the step kernel (MG_FUSE_STEP_OUT)
+    const MgFusion::Refresh r =
+        s->fuse.refresh(MG_PART_DOF, dst, dst_host, capture_id((hipStream_t)stream), s->layout.na > 0);
+    if (r.how == MG_REFRESH_SKIP) return MG_OK;   // written by the step kernel
     return refresh_rows(s, s->d_dof, s->layout.nd, 2, nullptr, s->layout.nd, dst, dst_host, (hipStream_t)stream);
 }
 
@@ -2052,23 +1998,15 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
     hipStream_t st = (hipStream_t)stream;
     const float* dsrc;
     const int* didx;
-    s->state_gen++;
-    const unsigned long long cid = capture_id(st);
-    s->last_set_deferred = 0;
-    if (!src_host && !idx && s->layout.roots_free && (s->fusion & MG_FUSE_ROOT_SET) && fuse_here(s, cid)) {
-        if (s->pend_root && s->pend_root_cap != cid)
-            if (int rc_ = flush_root(s, st)) return rc_;
-        s->pend_root = src;   // read by the next simulate (a later full set replaces it)
-        s->pend_root_cap = cid;
-        s->last_set_deferred = 1;
-        return MG_OK;
-    }
-    if (src_host && !idx && s->layout.roots_free && cid == 0) {
+    const MgFusion::Set f = s->fuse.set_root(src, src_host, idx != nullptr, s->layout.roots_free, capture_id(st));
+    if (int rc_ = apply_root(s, f.first, st)) return rc_;
+    if (f.how != MG_SET_NOW) s->set_st[0] = st;
+    if (f.how == MG_SET_DEFER) return MG_OK;   // read by the next simulate
+    if (f.how == MG_SET_DEFER_MAPPED) {
         // CPU pipeline, full set: copied at the call into the library's own buffer
         // (Isaac Gym's copy-at-set), read by the next simulate's step kernel like
         // a fused device set — or by the scatter a reader of the state issues first
         const size_t bytes = (size_t)s->layout.na * MG_STATE_N * sizeof(float);
-        s->pend_root = nullptr;     // a later full set replaces an earlier deferred one
         if (!s->h_root_in) {        // page-locked and device-mapped: the step kernel reads it over PCIe
             HostBuf<float> h;
             HIP_TRY(h.alloc(bytes / sizeof(float), true));
@@ -2079,11 +2017,9 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
         if (s->root_ev_pending) HIP_TRY(hipEventSynchronize(s->root_ev));   // its last reader is done
         s->root_ev_pending = false;
         std::memcpy(s->h_root_in, src, bytes);
-        s->pend_root = s->d_root_in_alias;
-        s->pend_root_cap = 0;
+        s->fuse.root_mapped(s->d_root_in_alias);
         return MG_OK;
     }
-    if (int rc_ = flush_root(s, st)) return rc_;
     int rc = stage_src(s, src, src_host, (size_t)s->layout.na * MG_STATE_N, idx, n_idx, st, &dsrc, &didx);
     if (rc) return rc;
     HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_actor_root, didx, idx ? n_idx : s->layout.na, s->layout.na,
@@ -2098,8 +2034,7 @@ int32_t mg_set_rigid_body_state(mg_sim* s, const float* src, int32_t src_host, v
     hipStream_t st = (hipStream_t)stream;
     const float* dsrc;
     const int* didx;
-    if (int rc_ = flush_root(s, st)) return rc_;
-    s->state_gen++;
+    if (int rc_ = apply_root(s, s->fuse.set_rigid_body(capture_id(st)), st)) return rc_;
     int rc = stage_src(s, src, src_host, (size_t)s->layout.nb * MG_STATE_N, nullptr, 0, st, &dsrc, &didx);
     if (rc) return rc;
     // free bodies only: rows are selected through the free-body list
@@ -2111,8 +2046,7 @@ int32_t mg_set_rigid_body_state(mg_sim* s, const float* src, int32_t src_host, v
 int32_t mg_set_dof_state(mg_sim* s, const float* src, int32_t src_host, const int32_t* idx, int32_t n_idx,
                          void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    s->dof_sgen++;
-    s->last_set_deferred = 0;
+    s->fuse.set_dof_state();
     return set_dof_columns(s, src, src_host, 2, s->d_dof, s->d_dof + s->layout.nd, idx, n_idx, (hipStream_t)stream);
 }
 // column k of the DOF targets; a device-resident full set is read by the next
@@ -2124,17 +2058,12 @@ static int32_t set_dof_target(mg_sim* s, int k, const float* src, int32_t src_ho
     if (!src) return fail(MG_ERR_ARG, "null source tensor");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->device));
-    const unsigned long long cid = capture_id(st);
-    s->last_set_deferred = 0;
-    if (!src_host && !idx && (s->fusion & MG_FUSE_DOF_TARGETS) && fuse_here(s, cid)) {
-        if (s->pend_tgt[k] && s->pend_tgt_cap[k] != cid)
-            if (int rc_ = flush_tgt(s, k, st)) return rc_;
-        s->pend_tgt[k] = src;
-        s->pend_tgt_cap[k] = cid;
-        s->last_set_deferred = 1;
+    const MgFusion::Set f = s->fuse.set_target(k, src, src_host, idx != nullptr, capture_id(st));
+    if (int rc_ = apply_tgt(s, k, f.first, st)) return rc_;
+    if (f.how == MG_SET_DEFER) {
+        s->set_st[1 + k] = st;
         return MG_OK;
     }
-    if (int rc_ = flush_tgt(s, k, st)) return rc_;
     return set_dof_columns(s, src, src_host, 1, s->d_dof_tgt + (size_t)k * s->layout.nd, nullptr, idx, n_idx, st);
 }
 int32_t mg_set_dof_position_target(mg_sim* s, const float* src, int32_t src_host, const int32_t* idx,

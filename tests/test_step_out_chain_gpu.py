@@ -260,6 +260,142 @@ def test_raised_fused_set_is_discarded(gym):
     assert torch.equal(outs[0], outs[1])
 
 
+def test_fusion_seams_between_eager_and_captured_servo(gym):
+    """The seams of step fusion the other tests do not cross (csrc/mg_fusion.h),
+    on 33 servo envs (one full wave and a one-lane tail): a STEP_FUSION_ALL sim
+    against an unfused one through the same calls, root, rigid-body and DOF
+    tensors equal bit for bit after each stage.
+    1. a deferred device root set made eagerly, then a simulate recorded into a
+       graph on a side stream: the set lands once, as an ordinary launch, and
+       the replays do not apply it again;
+    2. a device root set inside a capture with STEP_FUSION_IN_CAPTURE off;
+    3. a deferred root set followed by set_rigid_body_state_tensor before the
+       simulate;
+    4. the root tensor written (so rebound) between a simulate and its refresh."""
+    n = 33
+    acts = scenes.servo_actions(n, 6, DEV, seed=41)
+    sims = []
+    for fusion in (gymapi.STEP_FUSION_ALL, 0):
+        sim, _ = scenes.servo_scene(gym, n)
+        gym.prepare_sim(sim)
+        gym.set_step_fusion(sim, fusion)
+        sims.append((sim, _tensors(gym, sim)))
+    (sa, ta), (sb, tb) = sims
+    assert N.lib.mg_step_out_supported(sa.native) == 1
+    keep = []                                       # the sources a graph reads stay alive
+
+    def refresh(sim):
+        gym.refresh_actor_root_state_tensor(sim)
+        gym.refresh_rigid_body_state_tensor(sim)
+        gym.refresh_dof_state_tensor(sim)
+
+    def source(root, k):
+        src = root.clone()
+        src[:, 3:10] = acts[k]
+        keep.append(src)
+        return src
+
+    def same(what):
+        torch.cuda.synchronize()
+        for name, x, y in zip(("root", "rigid-body", "DOF"), ta, tb):
+            assert torch.equal(x, y), "%s: %s state differs" % (what, name)
+
+    def captured(body, replays):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                body()
+        torch.cuda.current_stream().wait_stream(side)
+        for _ in range(replays):
+            g.replay()
+        keep.append(g)
+
+    for sim, _ in sims:
+        refresh(sim)
+    same("initial state")
+    # 1. an eager deferred set, a captured simulate
+    for sim, (root, rb, dof) in sims:
+        assert gym.set_actor_root_state_tensor(sim, gymtorch.unwrap_tensor(source(root, 0)))
+        assert N.lib.mg_last_set_deferred(sim.native) == (1 if sim is sa else 0)
+        captured(lambda: (gym.simulate(sim), refresh(sim)), 3)
+    same("eager set, captured simulate, 3 replays")
+    # 2. a set inside a capture without IN_CAPTURE: an ordinary launch of the graph
+    gym.set_step_fusion(sa, gymapi.STEP_FUSION_ALL & ~gymapi.STEP_FUSION_IN_CAPTURE)
+    for sim, (root, rb, dof) in sims:
+        src = gymtorch.unwrap_tensor(source(root, 1))
+        captured(lambda: (gym.set_actor_root_state_tensor(sim, src), gym.simulate(sim), refresh(sim)), 2)
+        assert N.lib.mg_last_set_deferred(sim.native) == 0
+    same("captured set without IN_CAPTURE, 2 replays")
+    gym.set_step_fusion(sa, gymapi.STEP_FUSION_ALL)
+    # 3. a deferred root set, then a rigid-body set, then the simulate
+    for k in (2, 3):
+        for sim, (root, rb, dof) in sims:
+            refresh(sim)
+            assert gym.set_actor_root_state_tensor(sim, gymtorch.unwrap_tensor(source(root, k)))
+            assert N.lib.mg_last_set_deferred(sim.native) == (1 if sim is sa else 0)
+            bodies = rb.clone()
+            bodies[:, 7:10] += 0.25
+            assert gym.set_rigid_body_state_tensor(sim, gymtorch.unwrap_tensor(bodies))
+            assert N.lib.mg_last_set_deferred(sim.native) == 0
+            gym.simulate(sim)
+            refresh(sim)
+        same("root set, rigid-body set, simulate (%d)" % k)
+    # 4. the root tensor written between the simulate and its refresh
+    for k in (4, 5):
+        for sim, (root, rb, dof) in sims:
+            assert gym.set_actor_root_state_tensor(sim, gymtorch.unwrap_tensor(source(root, k)))
+            gym.simulate(sim)
+            root.fill_(-4.0)
+            refresh(sim)
+        same("root tensor written after the simulate (%d)" % k)
+        assert not torch.any(ta[0] == -4.0)
+    for sim, _ in sims:
+        gym.destroy_sim(sim)
+
+
+def test_eager_target_set_then_captured_simulate(gym):
+    """Seam 1 of the test above for a DOF target column: a deferred device target
+    set made eagerly, then a simulate recorded into a graph. 33 gimbals, fused
+    against unfused, DOF and rigid-body tensors bit for bit after 3 replays and
+    after one more eager step."""
+    n = 33
+    tg = scenes.gimbal_targets(n, 2, DEV, seed=43)
+    outs = []
+    for fusion in (gymapi.STEP_FUSION_ALL, 0):
+        sim, _ = scenes.gimbal_scene(gym, n)
+        gym.prepare_sim(sim)
+        gym.set_step_fusion(sim, fusion)
+        _, rb, dof = _tensors(gym, sim)
+        assert gym.set_dof_position_target_tensor(sim, gymtorch.unwrap_tensor(tg[0]))
+        assert N.lib.mg_last_set_deferred(sim.native) == (1 if fusion else 0)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                gym.simulate(sim)
+                gym.refresh_dof_state_tensor(sim)
+                gym.refresh_rigid_body_state_tensor(sim)
+        torch.cuda.current_stream().wait_stream(side)
+        for _ in range(3):
+            g.replay()
+        torch.cuda.synchronize()
+        outs.append((dof.clone(), rb.clone()))
+        assert gym.set_dof_position_target_tensor(sim, gymtorch.unwrap_tensor(tg[1]))
+        gym.simulate(sim)
+        gym.refresh_dof_state_tensor(sim)
+        gym.refresh_rigid_body_state_tensor(sim)
+        torch.cuda.synchronize()
+        outs.append((dof.clone(), rb.clone()))
+        gym.destroy_sim(sim)
+    for k in (0, 1):
+        assert torch.equal(outs[k][0], outs[2 + k][0]), "DOF state differs (%d)" % k
+        assert torch.equal(outs[k][1], outs[2 + k][1]), "rigid-body state differs (%d)" % k
+    assert not torch.equal(outs[0][0], outs[1][0])
+
+
 def test_gimbal_uniform_props_graph_replay(gym):
     """a hipGraph captured while every gimbal shared its DOF
     properties (k_artic_chain's wave-uniform constants) keeps stepping with the
