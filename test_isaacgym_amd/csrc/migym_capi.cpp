@@ -18,6 +18,7 @@
 #include "mg_chainlink.h"
 #include "mg_attractor.h"
 #include "mg_layout.h"
+#include "mg_route.h"
 #include "mg_fusion.h"
 
 thread_local MgKernelTimer* mg_timer = nullptr;
@@ -104,34 +105,19 @@ std::vector<T> to_soa(const T* aos, int n, int ncol) {
     return soa;
 }
 
-// an articulation group (mg_layout.h) with what later calls add to it
-struct ArticGroup : MgArticGroup {
-    ArticGroup() = default;
-    explicit ArticGroup(MgArticGroup&& g) : MgArticGroup(std::move(g)) {}
-    // k_artic_chain's shared constants (mg_chainlink.h): whether the stepped
-    // instances' DOF properties agree (upload and mg_set_dof_props), the
-    // constants themselves
+// what migym_capi.cpp adds to an articulation group of the layout plan (MgLayout::groups):
+// k_artic_chain's shared constants (mg_chainlink.h): whether the stepped
+// instances' DOF properties agree (upload and mg_set_dof_props), the
+// constants themselves
+struct ArticGroup {
     bool uni_dof = false;
     float uni[MG_CHAIN_UNI_N] = {};
-    // stepped instances that own an attractor (mg_set_attractors): rows
-    // step_offset .. of d_artic_split hold the other plain_count instances, then
-    // these attr_count (k_artic_lanes' attractor-aware build)
-    int attr_count = 0, plain_count = 0;
-    // stepped instances that hold a DOF with friction > 0 (jfr_route): rows
-    // step_offset .. of d_artic_jsplit hold the other jfr_plain instances, then
-    // these jfr_count (k_artic_lanes' joint-friction build); jfr_actor: the
-    // actor of the first of them, for a refusal's message
-    int jfr_count = 0, jfr_plain = 0, jfr_actor = -1;
 };
 
-// a coupled env group (mg_layout.h)
-struct EnvGroup : MgEnvGroup {
-    explicit EnvGroup(const MgEnvGroup& g) : MgEnvGroup(g) {}
-    // an env of the group holds a DOF with friction > 0 (jfr_route): the group
-    // steps in k_env_step's joint-friction build; jfr_actor: that DOF's actor
-    int jfr = 0, jfr_actor = -1;
-};
-
+static_assert(RS_G0 == MG_SENS_I_G0 && RS_LINK0 == MG_SENS_I_LINK0 && RS_LINK == MG_SENS_I_LINK && RS_MASK == MG_SENS_I_MASK &&
+              RS_FLAGS == MG_SENS_I_FLAGS && RS_ART == MG_SENS_I_ART && RS_OUT == MG_SENS_I_OUT && RS_HIST == MG_SENS_I_HIST &&
+              RS_OWNER == MG_SENS_I_OWNER && RS_I_N == MG_SENS_I_N && RS_F_N == MG_SENS_F_N && RS_ART_N == MG_SART_I_N,
+              "mg_route.h packs the force sensor tables in mg_internal.h's columns");
 static_assert(sizeof(MgSlotRec) == sizeof(std::array<int, 4>), "MgLayout::slot_rec is uploaded as MgSlotRec");
 // the device headers' constants the planner needs
 MgLayoutSizes layout_sizes() {
@@ -177,7 +163,7 @@ struct ModelBufs {
     DevBuf<float> d_link_f;
     DevBuf<int> d_link_i;
     DevBuf<int> d_artic_step;  // [..][4] instances stepped by k_artic_chain / k_artic_lanes
-    DevBuf<int> d_artic_jsplit;   // [step rows][MG_ARTIC_I_N] joint friction's split rows (jfr_commit)
+    DevBuf<int> d_artic_split; // [step rows][MG_ARTIC_I_N] the owners' split rows (MgRoute::split)
     DevBuf<int> d_env;         // [n_coupled][MG_ENV_I_N] coupled envs, by group
     DevBuf<int> d_pairs;       // [..][4] candidate shape pairs of the coupled envs
     DevBuf<float> d_fpatch;    // [pairs][MG_FP_N] friction patch records (coupled step, persistent)
@@ -206,18 +192,15 @@ inline int cap_rigid0(const MgLayout& L) { return L.n_pile + L.n_coupled; }
 inline int cap_units(const MgLayout& L) { return L.n_pile + L.n_coupled + (L.nf_rigid - L.nf1); }
 
 // What mg_upload_model builds apart and commits to the sim as one: the plan
-// (mg_layout.h: counts, storage order, index tables and the host mirrors later
-// calls read), its device buffers, and the groups. The plan's group lists move
-// into `groups` / `env_groups`, which carry what later calls add.
+// (mg_layout.h: counts, storage order, index tables, groups and the host mirrors
+// later calls read), its device buffers, what the groups carry besides, and the
+// routing plan of the step features (mg_route.h) with the DOF
+// property table it was planned from.
 struct Model : ModelBufs {
     MgLayout layout;
-    std::vector<ArticGroup> groups;
-    std::vector<EnvGroup> env_groups;
-    // joint friction's routing (jfr_commit): friction DOFs, instances in the
-    // lanes friction launches, envs of coupled friction groups; the host copy
-    // of d_artic_jsplit
-    int jfr_ndof = 0, jfr_lanes = 0, jfr_envs = 0;
-    std::vector<int> h_jsplit;
+    std::vector<ArticGroup> groups;   // by MgLayout::groups
+    MgRoute route;
+    std::vector<float> dof_props;     // [nd][MG_DOFPROP_N] as given
 };
 // the device form of the force sensor table (mg_set_force_sensors, MgSensorArgs)
 struct SensBufs {
@@ -304,54 +287,37 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     hipEvent_t rev_b = nullptr, rev_e = nullptr;
     bool rendered = false;
 
+    // Which launches the feature tables below imply, and what each carries, is
+    // Model::route (mg_route.h): every call that changes a table plans it anew.
+
     // rigid-body attractors (mg_set_attractors, mg_attractor.h). The table as
     // given; its device form (MG_ATTR_N floats per record, built in the
     // page-locked h_attr and sent by the next simulate when attr_dirty) and
-    // the internal slot -> record map; the routing it implies: per articulation
-    // group the stepped instances with and without an attractor (d_artic_split:
-    // the group's plain rows, then its attractor rows), the counts on free
-    // bodies and coupled envs' links, and the refusal mg_simulate reports
+    // the internal slot -> record map
     std::vector<mg_attractor> attrs;
     DevBuf<float> d_attr;
     DevBuf<int> d_attr_idx;            // [nb]
-    DevBuf<int> d_artic_split;         // [step rows][MG_ARTIC_I_N]
     HostBuf<float> h_attr;
     hipEvent_t attr_ev = nullptr;
     bool attr_ev_pending = false, attr_dirty = false;
-    int n_attr_free = 0, n_attr_env = 0;
-    std::string attr_err;
 
-    // joint friction: the routing the DOF property table
-    // implies (jfr_route, at upload and at every mg_set_dof_props). Friction
-    // DOFs, instances in the lanes friction launches, envs of coupled friction
-    // groups; the uncoupled groups' split rows on the device (d_artic_jsplit)
-    // and on the host
-    // (Model::jfr_*, h_jsplit)
-
-    // DOF force tensor (mg_enable_dof_forces): the step
-    // kernels' rows [nd], then the per-DOF reporting flags [nd] the refresh
-    // applies; the force-reporting builds step while dof_frc_n > 0
-    int dof_frc_n = 0;                    // DOFs of the actors that report
+    // DOF force tensor (mg_enable_dof_forces): d_dof_frc holds the
+    // step kernels' rows [nd], then the per-DOF reporting flags [nd] the refresh applies
 
     // force sensors (mg_set_force_sensors, mg_sensor.hip). The
-    // table as given and its device form (SensBufs), allocated by the first table
-    // with a sensor; sens_tmpl_env: templates whose coupled instances carry a
-    // sensor (their env groups step in k_env_step's contact-moment builds);
-    // sens_err: the refusal mg_simulate reports.
+    // table as given and its device form (SensBufs, from the route's host form),
+    // allocated by the first table with a sensor
     std::vector<mg_force_sensor> sensors;
-    std::vector<char> sens_tmpl_env;
-    std::string sens_err;
-    int n_sens = 0, n_sart = 0, sens_nhb = 0;
     DevBuf<float> d_ctorque;           // [3][nb], allocated with the first sensor table
 
     // rigid contact list (mg_set_contact_reporting, mg_contact.hip, DESIGN.md
-    // §3.14). While crep_on the reporting builds of the step kernels fill the
+    // §3.14). While route.crep the reporting builds of the step kernels fill the
     // staging records and k_contact_compact packs them into d_crep_out; the
     // buffers (CrepBufs) are allocated by the call that turns reporting on. crep_valid: a
     // reporting simulate has run since. The header (true total, stored total)
     // is kept on the device and in mapped host memory, which the refresh reads
     // after waiting for the stream.
-    bool crep_on = false, crep_valid = false;
+    bool crep_valid = false;
     int crep_capacity = 0;
     HostBuf<int> h_crep_hdr;            // [2] mapped, page-locked
     int* d_crep_hdr_alias = nullptr;      // its device address
@@ -620,33 +586,33 @@ int32_t mg_set_sim_params(mg_sim* s, const mg_sim_params* p) {
 // k_artic_chain's shared constants (mg_chainlink.h). Link mass constants and
 // the gravity flag of a group whose stepped instances agree on them
 // (MgArticGroup::uni_mass), from the first one's global rows.
-static void chain_uni_mass(const mg_model* m, ArticGroup& g) {
+static void chain_uni_mass(const mg_model* m, const MgArticGroup& g, ArticGroup& c) {
     const int b0 = g.step_body0[0];
     const float grav = m->tmpl_body_f[(size_t)m->body_tmpl[b0] * MG_TBODY_F_N + 4];
     for (int l = 1; l < g.nl; ++l) {
         const float* r = m->body_mass + (size_t)(b0 + l) * MG_MASS_N;
         const ChainLink k = chain_link_make(r[11], v3(r[8], r[9], r[10]), r[1], r[2], r[3], q4(r[4], r[5], r[6], r[7]));
-        float* u = g.uni + MG_CHAIN_UNI_LINK + 10 * (l - 1);
+        float* u = c.uni + MG_CHAIN_UNI_LINK + 10 * (l - 1);
         u[0] = k.m;
         u[1] = k.com.x; u[2] = k.com.y; u[3] = k.com.z;
         for (int j = 0; j < 6; ++j) u[4 + j] = k.ib[j];
     }
-    g.uni[MG_CHAIN_UNI_GRAV] = grav;
+    c.uni[MG_CHAIN_UNI_GRAV] = grav;
 }
 // DOF properties (global DOF order, MG_DOFPROP_N per DOF): fields 0..8 of each
 // DOF of the chain, when every stepped instance has the same
-static void chain_uni_dof(const float* props, ArticGroup& g) {
+static void chain_uni_dof(const float* props, const MgArticGroup& g, ArticGroup& c) {
     const int d0 = g.step_dof0[0];
     bool ok = true;
     for (size_t i = 1; i < g.step_dof0.size() && ok; ++i)
         for (int d = 0; d < g.ndof && ok; ++d)
             ok = std::memcmp(props + (size_t)(g.step_dof0[i] + d) * MG_DOFPROP_N, props + (size_t)(d0 + d) * MG_DOFPROP_N,
                              9 * sizeof(float)) == 0;
-    g.uni_dof = ok;
-    g.uni[MG_CHAIN_UNI_DOFOK] = ok ? 1.0f : 0.0f;   // read by the kernel (graph replays see changes)
+    c.uni_dof = ok;
+    c.uni[MG_CHAIN_UNI_DOFOK] = ok ? 1.0f : 0.0f;   // read by the kernel (graph replays see changes)
     if (!ok) return;
     for (int d = 0; d < g.ndof; ++d)
-        for (int j = 0; j < 9; ++j) g.uni[MG_CHAIN_UNI_DOF + 9 * d + j] = props[(size_t)(d0 + d) * MG_DOFPROP_N + j];
+        for (int j = 0; j < 9; ++j) c.uni[MG_CHAIN_UNI_DOF + 9 * d + j] = props[(size_t)(d0 + d) * MG_DOFPROP_N + j];
 }
 static hipError_t chain_uni_upload(Model* s) {
     if (!s->d_chain_uni) return hipSuccess;
@@ -656,128 +622,28 @@ static hipError_t chain_uni_upload(Model* s) {
     return hipMemcpy(s->d_chain_uni, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
 }
 
-// Joint friction routing of a DOF property table (global DOF
-// order, MG_DOFPROP_N per DOF, friction in field 9). Uncoupled instances that
-// hold a friction DOF step apart, in k_artic_lanes' joint-friction build (the
-// group's split rows: the plain instances, then these, as mg_set_attractors
-// lists attractor owners); a coupled group steps in k_env_step's joint-friction
-// build when any of its envs holds one. jfr_plan computes the routing and
-// changes nothing; jfr_commit installs it (fresh device rows) and cannot fail
-// after its allocation.
-struct JfrPlan {
-    int ndof = 0, lanes = 0, envs = 0;
-    std::vector<int> split;                    // empty: no lanes friction launch
-    std::vector<std::array<int, 3>> gc;        // per ArticGroup: plain, friction, actor
-    std::vector<std::array<int, 2>> ec;        // per EnvGroup: flag, actor
-    bool changed = false;
-};
-static int jfr_plan(const Model* s, const float* props, JfrPlan& pl) {
-    const int nd = s->layout.nd;
-    for (int d = 0; d < nd; ++d) {
-        const float f = props[(size_t)d * MG_DOFPROP_N + 9];
-        if (!(std::isfinite(f) && f >= 0.0f))
-            return fail(MG_ERR_ARG, "DOF %d: friction %g must be finite and non-negative", d, (double)f);
-        if (f > 0.0f) pl.ndof++;
-    }
-    auto fric_dof = [&](int d0, int n) {
-        for (int j = 0; j < n; ++j)
-            if (props[(size_t)(d0 + j) * MG_DOFPROP_N + 9] > 0.0f) return d0 + j;
-        return -1;
-    };
-    auto actor_of = [&](int d) {
-        const auto it = std::upper_bound(s->layout.actor_dof.begin(), s->layout.actor_dof.end(), d);
-        return (int)(it - s->layout.actor_dof.begin()) - 1;
-    };
-    pl.gc.assign(s->groups.size(), {0, 0, -1});
-    std::vector<std::vector<char>> owns(s->groups.size());
-    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-        const ArticGroup& g = s->groups[gi];
-        owns[gi].assign((size_t)g.step_count, 0);
-        for (int k = 0; pl.ndof > 0 && k < g.step_count; ++k) {
-            const int d = fric_dof(s->layout.artic_step[(size_t)(g.step_offset + k) * MG_ARTIC_I_N + 1], g.ndof);
-            if (d < 0) continue;
-            owns[gi][k] = 1;
-            pl.lanes++;
-            if (pl.gc[gi][2] < 0) pl.gc[gi][2] = actor_of(d);
-        }
-    }
-    if (pl.lanes > 0) {
-        pl.split.resize(s->layout.artic_step.size());
-        for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-            const ArticGroup& g = s->groups[gi];
-            int* dst = pl.split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
-            for (int pass = 0; pass < 2; ++pass)
-                for (int k = 0; k < g.step_count; ++k) {
-                    if ((owns[gi][k] != 0) != (pass == 1)) continue;
-                    std::memcpy(dst, s->layout.artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
-                                MG_ARTIC_I_N * sizeof(int));
-                    dst += MG_ARTIC_I_N;
-                    pl.gc[gi][pass]++;
-                }
-        }
-    }
-    pl.ec.assign(s->env_groups.size(), {0, -1});
-    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) {
-        const EnvGroup& g = s->env_groups[gi];
-        if (g.tmpl < 0 || pl.ndof == 0) continue;
-        for (int r = g.offset; r < g.offset + g.count && !pl.ec[gi][0]; ++r) {
-            const int d = fric_dof(s->layout.env_d0[r], g.ndof);
-            if (d >= 0) pl.ec[gi] = {1, actor_of(d)};
-        }
-        if (pl.ec[gi][0]) pl.envs += g.count;
-    }
-    pl.changed = pl.split != s->h_jsplit;
-    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) pl.changed = pl.changed || pl.ec[gi][0] != s->env_groups[gi].jfr;
+// ---- the routing plan of the step features (mg_route.h) ----
+// The sim's current feature tables as the planner's inputs; a call replaces the one it changes.
+static MgRouteIn route_in(const mg_sim* s) {
+    MgRouteIn in;
+    in.attrs = s->attrs.data(); in.n_attr = (int)s->attrs.size();
+    in.sensors = s->sensors.data(); in.n_sens = (int)s->sensors.size();
+    in.crep = s->route.crep;
+    in.dof_props = s->dof_props.empty() ? nullptr : s->dof_props.data();
+    in.dof_frc_n = s->route.dof_frc_n;
+    return in;
+}
+static int plan_route(const MgLayout& L, const MgRouteIn& in, MgRoute& R) {
+    std::string err;
+    if (int rc_ = mg_plan_route(L, in, R, err)) return fail(rc_, "%s", err.c_str());
     return MG_OK;
 }
-static int jfr_commit(Model* s, JfrPlan& pl) {
-    if (pl.changed) {
-        DevBuf<int> fresh;
-        if (!pl.split.empty() && fresh.upload(pl.split) != hipSuccess)
-            return fail(MG_ERR_DEVICE, "joint friction routing: copy failed");
-        // no step may still read the rows this replaces
-        if (hipDeviceSynchronize() != hipSuccess)
-            return fail(MG_ERR_DEVICE, "joint friction routing: device synchronize failed");
-        s->d_artic_jsplit = std::move(fresh);
-        s->h_jsplit.swap(pl.split);
-    }
-    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-        s->groups[gi].jfr_plain = pl.gc[gi][0];
-        s->groups[gi].jfr_count = pl.gc[gi][1];
-        s->groups[gi].jfr_actor = pl.gc[gi][2];
-    }
-    for (size_t gi = 0; gi < s->env_groups.size(); ++gi) {
-        s->env_groups[gi].jfr = pl.ec[gi][0];
-        s->env_groups[gi].jfr_actor = pl.ec[gi][1];
-    }
-    s->jfr_ndof = pl.ndof;
-    s->jfr_lanes = pl.lanes;
-    s->jfr_envs = pl.envs;
-    return MG_OK;
-}
-// friction together with a feature whose joint-friction build does not exist
-// (attractors, force sensors, contact reporting on the same group): the
-// refusal mg_simulate reports, or 0
-static int jfr_refusal(const mg_sim* s) {
-    for (const ArticGroup& g : s->groups)
-        if (g.jfr_count > 0 && g.attr_count > 0)
-            return fail(MG_ERR_UNSUPPORTED, "actor %d: joint friction (DOF friction > 0) together with an attractor on an "
-                        "articulation of the same group is not built", g.jfr_actor);
-    for (const EnvGroup& g : s->env_groups) {
-        if (!g.jfr) continue;
-        const char* what = nullptr;
-        if (s->crep_on) what = "contact reporting";
-        else if (s->n_sens > 0 && s->sens_tmpl_env[g.tmpl]) what = "a force sensor";
-        else if (s->n_attr_env > 0)
-            for (const mg_attractor& a : s->attrs) {
-                const int ar = s->layout.body_class[a.body] == ATTR_ENV_LINK ? s->layout.body_artic[a.body] : -1;
-                if (ar >= 0 && s->layout.artic_info[ar].tmpl == g.tmpl) what = "an attractor";
-            }
-        if (what)
-            return fail(MG_ERR_UNSUPPORTED, "actor %d: joint friction (DOF friction > 0) together with %s on the same "
-                        "coupled group is not built", g.jfr_actor, what);
-    }
-    return MG_OK;
+// `what` decides which kernels a simulate launches: a graph captured before the
+// call would replay the old launches
+static int refuse_captured(const mg_sim* s, const char* what, const char* verb = "call") {
+    if (!s->capturing) return MG_OK;
+    return fail(MG_ERR_STATE, "%s after the step was captured into a graph (the replays keep the old launches); %s it before "
+                "the capture, or after an eager simulate", what, verb);
 }
 
 // Plan, then commit: mg_plan_layout derives every table on
@@ -793,15 +659,18 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     if (int rc_ = mg_plan_layout(s->params, *m, layout_sizes(), L, err)) return fail(rc_, "%s", err.c_str());
     HIP_TRY(hipSetDevice(s->device));
     const int nb = L.nb, na = L.na, nd = L.nd;
-    for (MgArticGroup& g : L.groups) M.groups.emplace_back(std::move(g));
-    for (const MgEnvGroup& g : L.env_groups) M.env_groups.emplace_back(g);
-    L.groups.clear();
-    L.env_groups.clear();
-    for (ArticGroup& g : M.groups)
-        if (g.uni_mass) {
-            chain_uni_mass(m, g);
-            chain_uni_dof(m->dof_props, g);
+    M.groups.resize(L.groups.size());
+    for (size_t gi = 0; gi < L.groups.size(); ++gi)
+        if (L.groups[gi].uni_mass) {
+            chain_uni_mass(m, L.groups[gi], M.groups[gi]);
+            chain_uni_dof(m->dof_props, L.groups[gi], M.groups[gi]);
         }
+    // the step features' routing: no attractor, sensor or reporting yet; joint
+    // friction as the DOF property table has it
+    M.dof_props.assign(m->dof_props, m->dof_props + (size_t)nd * MG_DOFPROP_N);
+    MgRouteIn rin;
+    rin.dof_props = nd > 0 ? M.dof_props.data() : nullptr;
+    if (int rc_ = plan_route(L, rin, M.route)) return rc_;
 
     // bodies, templates, shapes
     HIP_TRY(M.d_state.upload(L.state0));
@@ -833,11 +702,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     // articulations
     HIP_TRY(M.d_chain_uni.alloc(std::max<size_t>(M.groups.size(), 1) * MG_CHAIN_UNI_N));
     HIP_TRY(chain_uni_upload(&M));
-    if (nd > 0) {   // joint friction: which kernels step the DOFs with friction > 0
-        JfrPlan pl;
-        if (int rc_ = jfr_plan(&M, m->dof_props, pl)) return rc_;
-        if (int rc_ = jfr_commit(&M, pl)) return rc_;
-    }
+    if (!M.route.split.empty()) HIP_TRY(M.d_artic_split.upload(M.route.split));
     HIP_TRY(M.d_artic.upload(L.artic_sorted));
     HIP_TRY(M.d_artic_step.upload(L.artic_step));
     HIP_TRY(M.d_link_f.upload(m->tmpl_link_f, (size_t)L.ntl * MG_LINK_F_N));
@@ -865,7 +730,6 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     std::vector<float>().swap(L.state0);
     std::vector<float>().swap(L.mass0);
     static_cast<Model&>(*s) = std::move(M);
-    s->dof_frc_n = 0;
     s->uploaded = true;
     return MG_OK;
 }
@@ -887,22 +751,18 @@ static void fused_targets(const mg_sim* s, const MgFusion::Step& fs, const float
 // the force sensor kernels' argument block (mg_sensor.hip)
 static MgSensorArgs sensor_args(const mg_sim* s, const MgStep& P) {
     MgSensorArgs A{};
-    A.n = s->n_sens; A.n_art = s->n_sart; A.nb = s->layout.nb; A.nd = s->layout.nd; A.nhb = s->sens_nhb;
+    const int n_sart = s->route.n_sart;
+    A.n = s->route.n_sens; A.n_art = n_sart; A.nb = s->layout.nb; A.nd = s->layout.nd; A.nhb = s->route.sens_nhb;
     A.sens_i = s->d_sens_i; A.sens_f = s->d_sens_f; A.sart_i = s->d_sart_i;
     A.perm = s->d_perm; A.link_i = s->d_link_i;
     A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl; A.tbf = s->d_tbf;
     A.ext = s->d_ext; A.cforce = s->d_cforce; A.ctorque = s->d_ctorque; A.dof = s->d_dof;
     A.hist = s->d_sens_hist; A.save = s->d_sens_save;
-    A.mark = s->d_sens_flag; A.valid = s->d_sens_flag + s->n_sart; A.parity = s->d_sens_flag + 2 * (size_t)s->n_sart;
+    A.mark = s->d_sens_flag; A.valid = s->d_sens_flag + n_sart; A.parity = s->d_sens_flag + 2 * (size_t)n_sart;
     A.out = s->d_sens_out;
     for (int k = 0; k < 3; ++k) A.g[k] = P.g[k];
     A.inv_dt = P.inv_dt;
     return A;
-}
-// This sim's step may write its rows itself (the fused refresh, the host stage): every kernel
-// that steps a body writes its rows, none is an attractor, reporting or joint-friction build.
-static bool step_writes_rows(const mg_sim* s) {
-    return s->layout.step_out_ok && s->attrs.empty() && !s->crep_on && s->jfr_ndof == 0;
 }
 
 // Where the step kernels write the refreshed rows themselves: the bound tensors
@@ -927,25 +787,21 @@ static StepOut step_out(const mg_sim* s, const MgFusion::Step& fs) {
     return O;
 }
 
-// The DOF force rows of a launch, or null: written while the sim reports DOF forces, and by every
-// contact-moment, reporting and joint-friction build (`feature`; the refresh masks the other rows).
-static float* dof_frc_rows(const mg_sim* s, bool feature) {
-    return s->dof_frc_n > 0 || feature ? s->d_dof_frc : nullptr;
-}
-
-// Group gi's launch over its plain instances (who 0), over those that hold a friction DOF (1)
-// or own an attractor (2): owners step apart (the group's split rows: the plain instances, then
-// these; rows loaded, not computed; a group with both kinds of owner is refused).
-static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
-    const ArticGroup& g = s->groups[gi];
+// The argument blocks of the route's launches (mg_route.h). A launch's feature pointers follow
+// its bits and nothing else.
+// An articulation group's launch: over all its stepped instances, or, in a group with owners
+// (l.split: rows loaded from the split table, not computed), over the plain ones, those that
+// hold a friction DOF or those that own an attractor.
+static MgArticArgs artic_args(mg_sim* s, const MgLaunch& l, const StepOut& O) {
+    const MgArticGroup& g = s->layout.groups[l.group];
     MgArticArgs A{};
     // the DOF part's validity is a flag in the block (MG_CHAIN_UNI_DOFOK), not
     // a launch choice: a captured launch follows later set_dof_props
-    A.uni = g.uni_mass ? s->d_chain_uni + gi * MG_CHAIN_UNI_N : nullptr;
-    A.na = g.step_count; A.nb = s->layout.nb; A.nd = s->layout.nd;
-    A.artic_i = s->d_artic_step + (size_t)g.step_offset * MG_ARTIC_I_N;
-    A.aff = g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
-    A.out_aff = g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
+    A.uni = g.uni_mass && !(l.feat & (RT_ATTR | RT_JFR)) ? s->d_chain_uni + (size_t)l.group * MG_CHAIN_UNI_N : nullptr;
+    A.na = l.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
+    A.artic_i = (l.split ? s->d_artic_split : s->d_artic_step) + (size_t)l.row0 * MG_ARTIC_I_N;
+    A.aff = l.split ? 0 : g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
+    A.out_aff = l.split ? 0 : g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
     A.tmpl = g.tmpl; A.nl = g.nl; A.ndof = g.ndof; A.fixed_base = g.fixed_base; A.chain = g.chain; A.nbl = g.nbody;
     A.link_f = s->d_link_f + (size_t)g.first_link * MG_LINK_F_N;
     A.link_i = s->d_link_i + (size_t)g.first_link * MG_LINK_I_N;
@@ -956,25 +812,11 @@ static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    A.dof_frc = dof_frc_rows(s, false);
+    A.dof_frc = l.feat & RT_FRC ? s->d_dof_frc : nullptr;
     A.out_rb = O.rb; A.out_root = O.root; A.out_dof = O.dof;   // chain groups only (s->layout.step_out_ok)
     A.out_body = O.out_body; A.out_root_row = O.out_root_row;
-    if (g.attr_count > 0 || g.jfr_count > 0) {
-        const int* split = g.jfr_count > 0 ? s->d_artic_jsplit : s->d_artic_split;
-        A.artic_i = split + (size_t)g.step_offset * MG_ARTIC_I_N;
-        A.na = g.jfr_count > 0 ? g.jfr_plain : g.plain_count;
-        A.aff = 0;
-        A.out_aff = 0;
-    }
-    if (who != 0) A.uni = nullptr;
-    if (who == 1) {
-        A.artic_i += (size_t)g.jfr_plain * MG_ARTIC_I_N;
-        A.na = g.jfr_count;
-        A.jfr = 1;
-        A.dof_frc = dof_frc_rows(s, true);
-    } else if (who == 2) {
-        A.artic_i += (size_t)g.plain_count * MG_ARTIC_I_N;
-        A.na = g.attr_count;
+    A.jfr = l.feat & RT_JFR ? 1 : 0;
+    if (l.feat & RT_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
@@ -982,7 +824,8 @@ static MgArticArgs artic_args(mg_sim* s, size_t gi, const StepOut& O, int who) {
 }
 
 // the coupled step of one env group (mg_env.hip)
-static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g, const MgFusion::Step& fs) {
+static MgEnvArgs env_args(mg_sim* s, const MgLaunch& l, const MgFusion::Step& fs) {
+    const MgEnvGroup& g = s->layout.env_groups[l.group];
     MgEnvArgs A{};
     A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
     A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
@@ -1008,26 +851,24 @@ static MgEnvArgs env_args(mg_sim* s, const EnvGroup& g, const MgFusion::Step& fs
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    // joint friction: attractors, sensors and reporting on this group were refused
-    A.jfr = g.jfr ? 1 : 0;
-    if (s->n_attr_env > 0 && !g.jfr) {
+    A.jfr = l.feat & RT_JFR ? 1 : 0;
+    if (l.feat & RT_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
-    if (s->crep_on) {   // the reporting builds
+    if (l.feat & RT_CREP) {   // the reporting builds
         A.crep = s->d_crep_cenv + g.offset;
         A.crep_n = s->d_crep_cenv_n + g.offset;
         A.crep_body = s->d_slot_global;
         A.crep_stride = std::max(s->layout.n_coupled, 1);
     }
-    // the contact-moment builds
-    if (s->n_sens > 0 && g.tmpl >= 0 && s->sens_tmpl_env[g.tmpl]) A.ctorque = s->d_ctorque;
-    A.dof_frc = dof_frc_rows(s, A.crep || A.ctorque || A.jfr);
+    if (l.feat & RT_SENS) A.ctorque = s->d_ctorque;   // the contact-moment builds
+    A.dof_frc = l.feat & RT_FRC ? s->d_dof_frc : nullptr;
     A.cap = {s->d_cap, s->d_cap_flags + cap_env0(s->layout) + g.offset};
     return A;
 }
 
-static MgPileArgs pile_args(const mg_sim* s) {
+static MgPileArgs pile_args(const mg_sim* s, const MgLaunch& l) {
     MgPileArgs A{};
     A.ne = s->layout.n_pile; A.nb = s->layout.nb;
     A.pile_i = s->d_pile_i; A.pile_body = s->d_pile_body; A.pairs = s->d_pile_pairs; A.slots = s->d_pile_slots;
@@ -1035,7 +876,7 @@ static MgPileArgs pile_args(const mg_sim* s) {
     A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    if (s->crep_on) {   // the reporting build
+    if (l.feat & RT_CREP) {   // the reporting build
         A.crep = s->d_crep_pile;
         A.crep_n = s->d_crep_pile_n;
         A.crep_body = s->d_slot_global;
@@ -1045,7 +886,7 @@ static MgPileArgs pile_args(const mg_sim* s) {
 }
 
 // the free-body step; a deferred root set (O.fs.root_src) is read by the kernel
-static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
+static MgRigidArgs rigid_args(const mg_sim* s, const MgLaunch& l, const StepOut& O) {
     MgRigidArgs A{};
     A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
     A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
@@ -1057,11 +898,11 @@ static MgRigidArgs rigid_args(const mg_sim* s, const StepOut& O) {
     A.gstride = std::max(s->layout.nf1, 1);
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    if (s->n_attr_free > 0) {
+    if (l.feat & RT_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
-    if (s->crep_on) {   // the reporting builds
+    if (l.feat & RT_CREP) {   // the reporting builds
         A.crep = s->d_crep_free;
         A.crep_n = s->d_crep_free_n;
         A.crep_body = s->d_slot_global;
@@ -1112,16 +953,14 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     s->capturing = cap != hipStreamCaptureStatusNone;
     // ---- refusals. Rigid-body attractors, sensors, joint friction: a table
     // this build cannot honour is refused, never ignored
-    if (!s->attr_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->attr_err.c_str());
-    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
-    if (s->jfr_ndof > 0)
-        if (int rc_ = jfr_refusal(s)) return rc_;
+    const MgRoute& R = s->route;
+    if (R.refusal) return fail(R.refusal, "%s", R.refusal_msg.c_str());
     if (s->attr_dirty && s->capturing)
         return fail(MG_ERR_STATE, "attractor table changed while the stream is being captured");
     // ---- begin: deferred sets this step's kernels do not read are applied as ordinary launches
     const unsigned long long cid = capture_id(st);
     const MgFusion::Begin fb =
-        s->fuse.begin_simulate(cid, s->layout.nf_rigid > 0, !s->groups.empty() || !s->env_groups.empty());
+        s->fuse.begin_simulate(cid, s->layout.nf_rigid > 0, !s->layout.groups.empty() || !s->layout.env_groups.empty());
     if (int rc_ = apply_root(s, fb.root, st)) return rc_;
     for (int k = 0; k < 3; ++k)
         if (int rc_ = apply_tgt(s, k, fb.tgt[k], st)) return rc_;
@@ -1148,7 +987,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
         timer.cap = mg_sim::kKern;
         mg_timer = &timer;
     }
-    if (s->n_sens > 0) {
+    if (R.n_sens > 0) {
         // force sensors: which articulations begin the frame with a state set
         // (a deferred root set is applied first, so that the comparison sees it)
         if (int rc_ = flush_root(s, st)) return rc_;
@@ -1158,40 +997,38 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // write the refreshed rows themselves where the ledger says: into the bound
     // tensors (MG_FUSE_STEP_OUT), else into the CPU pipeline's output stage
     // (mg_fetch_host_state: the library's own buffer, so no caller-visible tensor changes)
-    const MgFusion::Step fs = s->fuse.step(cid, step_writes_rows(s));
+    const MgFusion::Step fs = s->fuse.step(cid, R.step_writes_rows);
     const StepOut O = step_out(s, fs);
-    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-        const ArticGroup& g = s->groups[gi];
-        if (g.step_count == 0) continue;
-        const bool on[3] = {true, g.jfr_count > 0, g.attr_count > 0};
-        const char* const who[3] = {"", " (joint friction)", " (attractors)"};
-        for (int k = 0; k < 3; ++k) {
-            if (!on[k]) continue;
-            hipError_t e = mg_launch_artic_step(P, artic_args(s, gi, O, k), st);
-            if (e != hipSuccess)
-                return fail(MG_ERR_DEVICE, "articulation step launch%s: %s", who[k], hipGetErrorString(e));
+    for (const MgLaunch& l : R.launches) {
+        hipError_t e = hipSuccess;
+        switch (l.family) {
+            case MG_FAM_ARTIC:
+                e = mg_launch_artic_step(P, artic_args(s, l, O), st);
+                if (e != hipSuccess)
+                    return fail(MG_ERR_DEVICE, "articulation step launch%s: %s",
+                                l.feat & RT_JFR ? " (joint friction)" : l.feat & RT_ATTR ? " (attractors)" : "", hipGetErrorString(e));
+                break;
+            case MG_FAM_ENV:
+                e = mg_launch_env_step(P, env_args(s, l, fs), st);
+                if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
+                break;
+            case MG_FAM_PILE:
+                e = mg_launch_pile_step(P, pile_args(s, l), st);
+                if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
+                break;
+            default:
+                HIP_TRY(mg_launch_rigid_step(P, rigid_args(s, l, O), st, &s->rigid_form));
+                if (int rc_ = root_in_read(s, fs.root_src, st)) return rc_;
         }
-    }
-    for (const EnvGroup& g : s->env_groups) {
-        hipError_t e = mg_launch_env_step(P, env_args(s, g, fs), st);
-        if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
-    }
-    if (s->layout.n_pile > 0) {
-        hipError_t e = mg_launch_pile_step(P, pile_args(s), st);
-        if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
-    }
-    if (s->layout.nf_rigid > 0) {
-        HIP_TRY(mg_launch_rigid_step(P, rigid_args(s, O), st, &s->rigid_form));
-        if (int rc_ = root_in_read(s, fs.root_src, st)) return rc_;
     }
     // ---- end: the deferred sets were read (and the targets written through), the outputs written
     s->fuse.end_simulate(fs, cid);
-    if (s->crep_on) {
+    if (R.crep) {
         HIP_TRY(mg_launch_contact_compact(contact_args(s), st));
         s->crep_valid = true;
     }
     // the force sensors' readings, before the applied wrenches are cleared
-    if (s->n_sens > 0) HIP_TRY(mg_launch_force_sensor(sensor_args(s, P), st));
+    if (R.n_sens > 0) HIP_TRY(mg_launch_force_sensor(sensor_args(s, P), st));
     if (s->ext_pending) {
         HIP_TRY(hipMemsetAsync(s->d_ext, 0, (size_t)s->layout.nb * 6 * sizeof(float), st));
         s->ext_pending = false;
@@ -1293,75 +1130,20 @@ static void attr_record(const mg_attractor& a, float* r) {
 int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (n < 0 || (n > 0 && !host)) return fail(MG_ERR_ARG, "bad attractor table");
-    // the table decides which kernels a simulate launches: a graph captured
-    // before the call would replay the old launches
-    if (s->capturing)
-        return fail(MG_ERR_STATE, "attractor table changed after the step was captured into a graph (the replays keep "
-                    "the old launches); call it before the capture, or after an eager simulate");
+    if (int rc_ = refuse_captured(s, "attractor table changed")) return rc_;
     HIP_TRY(hipSetDevice(s->device));
-    std::vector<int> idx((size_t)std::max(s->layout.nb, 1), -1);   // internal slot -> record
-    for (int i = 0; i < n; ++i) {
-        const mg_attractor& a = host[i];
-        if (a.body < 0 || a.body >= s->layout.nb) return fail(MG_ERR_ARG, "attractor %d: body %d out of range", i, a.body);
-        if (!(std::isfinite(a.stiffness) && a.stiffness >= 0.0f && std::isfinite(a.damping) && a.damping >= 0.0f))
-            return fail(MG_ERR_ARG, "attractor %d: stiffness and damping must be finite and non-negative", i);
-        bool fin = true;
-        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(a.offset_p[k]) && std::isfinite(a.target_p[k]);
-        for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(a.offset_q[k]) && std::isfinite(a.target_q[k]);
-        if (!fin) return fail(MG_ERR_ARG, "attractor %d: offset and target must be finite", i);
-        const int slot = s->layout.perm[a.body];
-        if (idx[slot] >= 0)
-            return fail(MG_ERR_UNSUPPORTED, "attractor %d: body %d already owns attractor %d (one attractor per body)",
-                        i, a.body, idx[slot]);
-        idx[slot] = i;
-    }
-    // what steps each body: the routing, or the refusal mg_simulate reports
-    std::string err;
-    int nfree = 0, nenv = 0, nartic = 0;
-    std::vector<std::vector<char>> owns(s->groups.size());
-    for (size_t gi = 0; gi < s->groups.size(); ++gi) owns[gi].assign((size_t)s->groups[gi].step_count, 0);
-    for (int i = 0; i < n; ++i) {
-        const int b = host[i].body;
-        const char* why = nullptr;
-        switch (s->layout.body_class[b]) {
-            case ATTR_FREE: nfree++; break;
-            case ATTR_ENV_LINK: nenv++; break;
-            case ATTR_LINK: nartic++; owns[s->layout.body_grp[b]][s->layout.body_inst[b]] = 1; break;
-            case ATTR_ENV_FREE: why = "a free body of a coupled env"; break;
-            case ATTR_PILE: why = "a body of a pile env"; break;
-            default: why = "not a dynamic body"; break;
-        }
-        if (why && err.empty()) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "attractor %d on rigid body %d: %s cannot carry an attractor in this build", i, b,
-                     why);
-            err = buf;
-        }
-    }
-    // the new state is built apart — host vectors, fresh device buffers — and
-    // committed at the end, so an error leaves the sim's table as it was
-    std::vector<int> split;
-    std::vector<std::pair<int, int>> counts(s->groups.size(), {0, 0});   // plain, owners
-    if (nartic > 0) {
-        split.resize(s->layout.artic_step.size());
-        for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-            const ArticGroup& g = s->groups[gi];
-            int* dst = split.data() + (size_t)g.step_offset * MG_ARTIC_I_N;
-            for (int pass = 0; pass < 2; ++pass)
-                for (int k = 0; k < g.step_count; ++k) {
-                    if ((owns[gi][k] != 0) != (pass == 1)) continue;
-                    std::memcpy(dst, s->layout.artic_step.data() + (size_t)(g.step_offset + k) * MG_ARTIC_I_N,
-                                MG_ARTIC_I_N * sizeof(int));
-                    dst += MG_ARTIC_I_N;
-                    (pass ? counts[gi].second : counts[gi].first)++;
-                }
-        }
-    }
+    // the table is checked and routed (or its refusal kept for mg_simulate) by the plan
+    MgRouteIn in = route_in(s);
+    in.attrs = host; in.n_attr = n;
+    MgRoute R;
+    if (int rc_ = plan_route(s->layout, in, R)) return rc_;
+    // the new state is built apart — fresh device buffers — and committed at the
+    // end, so an error leaves the sim's table as it was
     DevBuf<int> d_idx, d_split;   // freed unless committed
     DevBuf<float> d_attr;
     HostBuf<float> h_attr;
-    HIP_TRY(d_idx.upload(idx));
-    if (!split.empty()) HIP_TRY(d_split.upload(split));
+    HIP_TRY(d_idx.upload(R.attr_idx));
+    if (!R.split.empty()) HIP_TRY(d_split.upload(R.split));
     if (n > 0) {
         HIP_TRY(d_attr.alloc((size_t)n * MG_ATTR_N));
         HIP_TRY(h_attr.alloc((size_t)n * MG_ATTR_N, false));
@@ -1376,14 +1158,8 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     s->d_artic_split = std::move(d_split);
     s->d_attr = std::move(d_attr);
     s->h_attr = std::move(h_attr);
-    for (size_t gi = 0; gi < s->groups.size(); ++gi) {
-        s->groups[gi].plain_count = counts[gi].first;
-        s->groups[gi].attr_count = counts[gi].second;
-    }
     s->attrs.assign(host, host + n);
-    s->n_attr_free = nfree;
-    s->n_attr_env = nenv;
-    s->attr_err = err;
+    s->route = std::move(R);
     s->attr_dirty = n > 0;
     return MG_OK;
 }
@@ -1464,14 +1240,14 @@ int32_t mg_discard_pending_sets(mg_sim* s) {
     return MG_OK;
 }
 
-int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && step_writes_rows(s) ? 1 : 0; }
+int32_t mg_step_out_supported(mg_sim* s) { return s && s->uploaded && s->route.step_writes_rows ? 1 : 0; }
 
 int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (!out) return fail(MG_ERR_ARG, "null output");
-    out[0] = s->jfr_ndof;
-    out[1] = s->jfr_lanes;
-    out[2] = s->jfr_envs;
+    out[0] = s->route.jfr_ndof;
+    out[1] = s->route.jfr_lanes;
+    out[2] = s->route.jfr_envs;
     return MG_OK;
 }
 
@@ -1598,12 +1374,12 @@ int32_t mg_debug_copy_env_ctab(mg_sim* s, int32_t k, float* dst, int32_t cap) {
 // facts that choose its chain-kernel form (mg_chain.hip mg_launch_artic_chain)
 int32_t mg_debug_artic_groups(mg_sim* s, int32_t* out, int32_t cap) {
     if (!s || !s->uploaded || (!out && cap > 0)) return fail(MG_ERR_ARG, "bad arguments");
-    const int32_t n = (int32_t)s->groups.size();
+    const int32_t n = (int32_t)s->layout.groups.size();
     for (int32_t i = 0; i < n && (i + 1) * MG_DEBUG_GROUP_N <= cap; ++i) {
-        const ArticGroup& g = s->groups[i];
+        const MgArticGroup& g = s->layout.groups[i];
         int32_t* r = out + (size_t)i * MG_DEBUG_GROUP_N;
         r[0] = g.nl; r[1] = g.step_count; r[2] = g.chain; r[3] = g.uni_mass ? 1 : 0;
-        r[4] = g.uni_dof ? 1 : 0; r[5] = g.aff; r[6] = g.out_aff; r[7] = s->layout.step_out_ok ? 1 : 0;
+        r[4] = s->groups[i].uni_dof ? 1 : 0; r[5] = g.aff; r[6] = g.out_aff; r[7] = s->layout.step_out_ok ? 1 : 0;
     }
     return n;
 }
@@ -1728,11 +1504,7 @@ int32_t mg_enable_dof_forces(mg_sim* s, const int32_t* actor_on, int32_t n_actor
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (actor_on && n_actors != s->layout.na)
         return fail(MG_ERR_ARG, "DOF force flags for %d actors, the model has %d", n_actors, s->layout.na);
-    // the flags decide which kernels a simulate launches: a graph captured
-    // before the call would replay the old launches
-    if (s->capturing)
-        return fail(MG_ERR_STATE, "DOF force reporting changed after the step was captured into a graph (the replays "
-                    "keep the old launches); call it before the capture, or after an eager simulate");
+    if (int rc_ = refuse_captured(s, "DOF force reporting changed")) return rc_;
     HIP_TRY(hipSetDevice(s->device));
     std::vector<float> on((size_t)std::max(s->layout.nd, 1), 0.0f);
     int n = 0;
@@ -1740,13 +1512,17 @@ int32_t mg_enable_dof_forces(mg_sim* s, const int32_t* actor_on, int32_t n_actor
         for (int a = 0; a < s->layout.na; ++a)
             if (actor_on[a])
                 for (int d = s->layout.actor_dof[a]; d < s->layout.actor_dof[a + 1]; ++d) { on[d] = 1.0f; ++n; }
+    MgRouteIn in = route_in(s);
+    in.dof_frc_n = n;
+    MgRoute R;
+    if (int rc_ = plan_route(s->layout, in, R)) return rc_;
     // rows of actors that stop reporting, or that no kernel steps, read 0
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemset(s->d_dof_frc, 0, (size_t)std::max(s->layout.nd, 1) * sizeof(float)));
     if (s->layout.nd > 0)
         HIP_TRY(hipMemcpy(s->d_dof_frc + s->layout.nd, on.data(), (size_t)s->layout.nd * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
-    s->dof_frc_n = n;
+    s->route = std::move(R);
     return MG_OK;
 }
 
@@ -1767,132 +1543,49 @@ int32_t mg_refresh_dof_force(mg_sim* s, float* dst, int32_t dst_host, void* stre
     return MG_OK;
 }
 
-int32_t mg_num_dof_force_dofs(mg_sim* s) { return s ? s->dof_frc_n : 0; }
+int32_t mg_num_dof_force_dofs(mg_sim* s) { return s ? s->route.dof_frc_n : 0; }
 
 // ---- force sensors -------------------------------------------
 int32_t mg_set_force_sensors(mg_sim* s, const mg_force_sensor* host, int32_t n) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (n < 0 || (n > 0 && !host)) return fail(MG_ERR_ARG, "bad force sensor table");
-    // the table decides which kernels a simulate launches: a graph captured
-    // before the call would replay the old launches
-    if (s->capturing)
-        return fail(MG_ERR_STATE, "force sensor table changed after the step was captured into a graph (the replays "
-                    "keep the old launches); call it before the capture, or after an eager simulate");
+    if (int rc_ = refuse_captured(s, "force sensor table changed")) return rc_;
     HIP_TRY(hipSetDevice(s->device));
-    std::string err;
-    for (int i = 0; i < n; ++i) {
-        const mg_force_sensor& f = host[i];
-        if (f.body < 0 || f.body >= s->layout.nb) return fail(MG_ERR_ARG, "force sensor %d: body %d out of range", i, f.body);
-        bool fin = true;
-        float q2 = 0.0f;
-        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(f.p[k]);
-        for (int k = 0; k < 4; ++k) { fin = fin && std::isfinite(f.q[k]); q2 += f.q[k] * f.q[k]; }
-        if (!fin || !(q2 > 0.0f)) return fail(MG_ERR_ARG, "force sensor %d: the local pose must be finite, its rotation not zero", i);
-        if (s->layout.body_artic[f.body] < 0 && err.empty()) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "force sensor %d on rigid body %d: a single-body actor has no joint to measure "
-                     "(and the free-body and pile kernels keep no contact moment); force sensors sit on bodies of "
-                     "articulations", i, f.body);
-            err = buf;
-        }
-    }
-    // lanes: sensor slot (its place among its articulation's sensors) major,
-    // articulation minor, templates apart — neighbouring lanes read
-    // neighbouring instances
-    struct Lane { int tmpl, slot, art, row; };
-    std::vector<Lane> lanes;
-    std::vector<int> art_slot(s->layout.artic_info.size(), 0), art_id(s->layout.artic_info.size(), -1);
-    std::vector<int> sart, hist0;
-    std::vector<char> tmpl_env(s->layout.atmpl.size() / MG_ATMPL_I_N, 0);
-    int nhb = 0, nsave = 0;
-    if (err.empty())
-        for (int i = 0; i < n; ++i) {
-            const int a = s->layout.body_artic[host[i].body];
-            const MgArticInfo& ai = s->layout.artic_info[a];
-            if (art_id[a] < 0) {
-                art_id[a] = (int)hist0.size();
-                const int ndof = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 2];
-                const int nl = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 1], l0 = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 0];
-                int nbody = 0;
-                for (int l = 0; l < nl; ++l) nbody += s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] >= 0 ? 1 : 0;
-                const int row[MG_SART_I_N] = {s->layout.perm[ai.g0], ai.d0, ndof, nsave};
-                sart.insert(sart.end(), row, row + MG_SART_I_N);
-                hist0.push_back(nhb);
-                nhb += nbody;
-                nsave += MG_STATE_N + 2 * ndof;
-                if (ai.coupled) tmpl_env[ai.tmpl] = 1;
-            }
-            lanes.push_back({ai.tmpl, art_slot[a]++, art_id[a], i});
-        }
-    std::stable_sort(lanes.begin(), lanes.end(), [](const Lane& x, const Lane& y) {
-        return x.tmpl != y.tmpl ? x.tmpl < y.tmpl : (x.slot != y.slot ? x.slot < y.slot : x.art < y.art);
-    });
-    const int nl_ = (int)lanes.size(), nart = (int)hist0.size();
-    std::vector<int> si((size_t)MG_SENS_I_N * std::max(nl_, 1), 0);
-    std::vector<float> sf((size_t)MG_SENS_F_N * std::max(nl_, 1), 0.0f);
-    for (int t = 0; t < nl_; ++t) {
-        const Lane& L = lanes[t];
-        const mg_force_sensor& f = host[L.row];
-        const MgArticInfo& ai = s->layout.artic_info[s->layout.body_artic[f.body]];
-        const int l0 = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 0], nl = s->layout.atmpl[ai.tmpl * MG_ATMPL_I_N + 1];
-        // the sensor body's link, and its subtree (links in topological order:
-        // a link joins when its parent is in)
-        int ls = -1;
-        for (int l = 0; l < nl; ++l)
-            if (s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 3] == f.body - ai.g0) ls = l;
-        if (ls < 0) return fail(MG_ERR_ARG, "force sensor %d: body %d is no link of its articulation", L.row, f.body);
-        unsigned mask = 1u << ls;
-        for (int l = ls + 1; l < nl; ++l) {
-            const int p = s->layout.link_i[(size_t)(l0 + l) * MG_LINK_I_N + 0];
-            if (p >= 0 && ((mask >> p) & 1u)) mask |= 1u << l;
-        }
-        si[(size_t)MG_SENS_I_G0 * nl_ + t] = ai.g0;
-        si[(size_t)MG_SENS_I_LINK0 * nl_ + t] = l0;
-        si[(size_t)MG_SENS_I_LINK * nl_ + t] = ls;
-        si[(size_t)MG_SENS_I_MASK * nl_ + t] = (int)mask;
-        si[(size_t)MG_SENS_I_FLAGS * nl_ + t] = f.flags & (MG_SENSOR_FORWARD | MG_SENSOR_CONSTRAINT | MG_SENSOR_WORLD);
-        si[(size_t)MG_SENS_I_ART * nl_ + t] = L.art;
-        si[(size_t)MG_SENS_I_OUT * nl_ + t] = L.row;
-        si[(size_t)MG_SENS_I_HIST * nl_ + t] = hist0[L.art];
-        si[(size_t)MG_SENS_I_OWNER * nl_ + t] = L.slot == 0 ? 1 : 0;
-        const float qn = 1.0f / std::sqrt(f.q[0] * f.q[0] + f.q[1] * f.q[1] + f.q[2] * f.q[2] + f.q[3] * f.q[3]);
-        for (int k = 0; k < 3; ++k) sf[(size_t)k * nl_ + t] = f.p[k];
-        for (int k = 0; k < 4; ++k) sf[(size_t)(3 + k) * nl_ + t] = f.q[k] * qn;
-    }
+    // the table is checked, packed for the kernels and routed (or its refusal kept) by the plan
+    MgRouteIn in = route_in(s);
+    in.sensors = host; in.n_sens = n;
+    MgRoute R;
+    if (int rc_ = plan_route(s->layout, in, R)) return rc_;
     // fresh device buffers, committed at the end: an error leaves the table as it was
     HIP_TRY(hipDeviceSynchronize());
     SensBufs B;
-    if (nl_ > 0) {
-        hipError_t e = B.d_sens_i.upload(si);
-        if (e == hipSuccess) e = B.d_sens_f.upload(sf);
-        if (e == hipSuccess) e = B.d_sart_i.upload(sart);
+    if (R.n_sens > 0) {
+        hipError_t e = B.d_sens_i.upload(R.si);
+        if (e == hipSuccess) e = B.d_sens_f.upload(R.sf);
+        if (e == hipSuccess) e = B.d_sart_i.upload(R.sart);
         // no frame held yet: every articulation's first frame reads 0
-        if (e == hipSuccess) e = B.d_sens_flag.zero((size_t)2 * nart + 1);
-        if (e == hipSuccess) e = B.d_sens_hist.zero((size_t)12 * nhb);
-        if (e == hipSuccess) e = B.d_sens_save.zero((size_t)nsave);
-        if (e == hipSuccess) e = B.d_sens_out.zero((size_t)6 * nl_);
+        if (e == hipSuccess) e = B.d_sens_flag.zero((size_t)2 * R.n_sart + 1);
+        if (e == hipSuccess) e = B.d_sens_hist.zero((size_t)12 * R.sens_nhb);
+        if (e == hipSuccess) e = B.d_sens_save.zero((size_t)R.sens_nsave);
+        if (e == hipSuccess) e = B.d_sens_out.zero((size_t)6 * R.n_sens);
         if (e == hipSuccess && !s->d_ctorque) e = s->d_ctorque.zero((size_t)3 * std::max(s->layout.nb, 1));
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) return fail(MG_ERR_DEVICE, "force sensor table: %s", hipGetErrorString(e));
     }
     static_cast<SensBufs&>(*s) = std::move(B);
     s->sensors.assign(host, host + n);
-    s->n_sens = nl_;
-    s->n_sart = nart;
-    s->sens_nhb = nhb;
-    s->sens_tmpl_env = tmpl_env;
-    s->sens_err = err;
+    s->route = std::move(R);
     return MG_OK;
 }
 
 int32_t mg_refresh_force_sensor(mg_sim* s, float* dst, int32_t dst_host, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
-    if (!s->sens_err.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->sens_err.c_str());
-    if (s->n_sens == 0) return MG_OK;
+    if (!s->route.sens_refusal.empty()) return fail(MG_ERR_UNSUPPORTED, "%s", s->route.sens_refusal.c_str());
+    if (s->route.n_sens == 0) return MG_OK;
     if (!dst) return fail(MG_ERR_ARG, "null destination");
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)s->n_sens * 6 * sizeof(float);
+    const size_t bytes = (size_t)s->route.n_sens * 6 * sizeof(float);
     HIP_TRY(hipMemcpyAsync(dst, s->d_sens_out, bytes, dst_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (dst_host) HIP_TRY(hipStreamSynchronize(st));
     return MG_OK;
@@ -1904,15 +1597,17 @@ int32_t mg_num_force_sensors(mg_sim* s) { return s ? (int32_t)s->sensors.size() 
 int32_t mg_set_contact_reporting(mg_sim* s, int32_t on, int32_t capacity) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (capacity < 0) return fail(MG_ERR_ARG, "negative contact capacity %d", capacity);
-    // the switch decides which kernels a simulate launches: a graph captured
-    // before the call would replay the old launches
-    if (s->capturing)
-        return fail(MG_ERR_STATE, "contact reporting changed after the step was captured into a graph (the replays "
-                    "keep the old launches); call it before the capture, or after an eager simulate");
+    if (int rc_ = refuse_captured(s, "contact reporting changed")) return rc_;
     HIP_TRY(hipSetDevice(s->device));
+    MgRouteIn in = route_in(s);
+    MgRoute R_off, R_on;
+    in.crep = false;
+    if (int rc_ = plan_route(s->layout, in, R_off)) return rc_;
+    in.crep = true;
+    if (int rc_ = plan_route(s->layout, in, R_on)) return rc_;
     HIP_TRY(hipDeviceSynchronize());
     static_cast<CrepBufs&>(*s) = CrepBufs();
-    s->crep_on = false;
+    s->route = std::move(R_off);
     s->crep_valid = false;
     s->crep_capacity = 0;
     if (!on) return MG_OK;
@@ -1954,18 +1649,18 @@ int32_t mg_set_contact_reporting(mg_sim* s, int32_t on, int32_t capacity) {
     HIP_TRY(hipDeviceSynchronize());
     static_cast<CrepBufs&>(*s) = std::move(B);
     s->crep_capacity = cap;
-    s->crep_on = true;
+    s->route = std::move(R_on);
     return MG_OK;
 }
 
-int32_t mg_contact_reporting(mg_sim* s) { return s && s->crep_on ? 1 : 0; }
+int32_t mg_contact_reporting(mg_sim* s) { return s && s->route.crep ? 1 : 0; }
 
 int32_t mg_refresh_rigid_contacts(mg_sim* s, mg_rigid_contact* dst, int32_t cap, int32_t dst_host, int32_t* total,
                                   void* stream) {
     if (total) *total = 0;
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (cap < 0 || (!dst && cap > 0)) return fail(MG_ERR_ARG, "bad destination");
-    if (!s->crep_on || !s->crep_valid) return 0;
+    if (!s->route.crep || !s->crep_valid) return 0;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2084,20 +1779,29 @@ int32_t mg_set_dof_props(mg_sim* s, const float* props_host) {
     if (s->layout.nd == 0) return MG_OK;
     if (!props_host) return fail(MG_ERR_ARG, "null props");
     HIP_TRY(hipSetDevice(s->device));
-    // joint friction: the table decides which kernels a simulate launches (a
-    // graph captured before the call would replay the old launches); the new
-    // routing is built apart and committed after the table itself is copied
-    JfrPlan pl;
-    if (int rc_ = jfr_plan(s, props_host, pl)) return rc_;
-    if (pl.changed && s->capturing)
-        return fail(MG_ERR_STATE, "DOF friction changed which kernels step the DOFs after the step was captured into a "
-                    "graph (the replays keep the old launches); set it before the capture, or after an eager simulate");
+    // joint friction: the new routing is built apart and committed after the
+    // table itself is copied; only a table that changes it needs the device idle
+    std::vector<float> props(props_host, props_host + (size_t)s->layout.nd * MG_DOFPROP_N);
+    MgRouteIn in = route_in(s);
+    in.dof_props = props.data();
+    MgRoute R;
+    if (int rc_ = plan_route(s->layout, in, R)) return rc_;
+    const bool changed = !R.same_launches(s->route);
+    if (changed)
+        if (int rc_ = refuse_captured(s, "DOF friction changed which kernels step the DOFs", "set")) return rc_;
     std::vector<float> dp = to_soa(props_host, s->layout.nd, MG_DOFPROP_N);
-    if (pl.changed) HIP_TRY(hipDeviceSynchronize());   // the old launches read the old table to their end
+    DevBuf<int> d_split;
+    if (changed) {
+        if (!R.split.empty() && d_split.upload(R.split) != hipSuccess)
+            return fail(MG_ERR_DEVICE, "joint friction routing: copy failed");
+        HIP_TRY(hipDeviceSynchronize());   // the old launches read the old table and rows to their end
+    }
     HIP_TRY(hipMemcpy(s->d_dof_props, dp.data(), dp.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc_ = jfr_commit(s, pl)) return rc_;
-    for (ArticGroup& g : s->groups)
-        if (g.uni_mass) chain_uni_dof(props_host, g);
+    s->dof_props.swap(props);
+    if (changed) s->d_artic_split = std::move(d_split);
+    s->route = std::move(R);
+    for (size_t gi = 0; gi < s->groups.size(); ++gi)
+        if (s->layout.groups[gi].uni_mass) chain_uni_dof(props_host, s->layout.groups[gi], s->groups[gi]);
     HIP_TRY(chain_uni_upload(s));
     return MG_OK;
 }
@@ -2126,8 +1830,8 @@ int32_t mg_apply_rigid_body_force(mg_sim* s, const float* force, const float* to
 static int refresh_jac_mm(mg_sim* s, int32_t tmpl, float* jdst, float* mdst, int32_t dst_host, void* stream) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
     if (!jdst && !mdst) return fail(MG_ERR_ARG, "null destination");
-    const ArticGroup* g = nullptr;
-    for (const ArticGroup& x : s->groups)
+    const MgArticGroup* g = nullptr;
+    for (const MgArticGroup& x : s->layout.groups)
         if (x.tmpl == tmpl) g = &x;
     if (!g) return fail(MG_ERR_ARG, "no articulation template %d", tmpl);
     const int nc = g->ndof + (g->fixed_base ? 0 : 6);
