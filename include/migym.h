@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 1
+#define MG_ABI_VERSION 2
 
 /* status codes */
 #define MG_OK              0
@@ -701,6 +701,26 @@ int32_t     mg_num_articulations(mg_sim* sim);
 #define MG_RIGID_FORM_REC  2
 #define MG_RIGID_FORM_BOX  4
 int32_t     mg_last_rigid_form(mg_sim* sim);
+/* Diagnostics: the step kernel builds the last simulate launched, in launch
+ * order, as rows of MG_STEP_BUILD_N int32: the kernel (MG_KERNEL_*), its integer
+ * template parameter (the chains' links NL; k_env_step's and k_artic_lanes'
+ * links MAXL, whose lane count follows: 64 above 16, else 16; k_rigid_step's
+ * contact slots; else 0) and its form word (csrc/mg_forms.h). A coupled group
+ * is one row (its narrow phase and its substeps repeat the same build); the
+ * free bodies are up to two (single-shape, then multi-shape). These are the
+ * records mg_simulate launched from, not a second account of them:
+ * mg_last_rigid_form reads the same ones. Writes at most `cap` rows to `out`
+ * (which may be null when cap is 0) and returns the number of rows the
+ * simulate made; < 0 on error. */
+#define MG_KERNEL_RIGID_STEP1   1
+#define MG_KERNEL_RIGID_STEP    2
+#define MG_KERNEL_ARTIC_CHAIN   3
+#define MG_KERNEL_ARTIC_CHAIN_Q 4
+#define MG_KERNEL_ARTIC_LANES   5
+#define MG_KERNEL_ENV_STEP      6
+#define MG_KERNEL_PILE_STEP     7
+#define MG_STEP_BUILD_N         3
+int32_t     mg_debug_step_builds(mg_sim* sim, int32_t* out, int32_t cap);
 /* Diagnostics: out[i] = 1.0f / d[i] for n floats of device memory (both device
  * pointers, on the current device), computed two at a time by the paired
  * reciprocal the one-round free-body step forms its rows' effective masses

@@ -35,6 +35,10 @@ MG_DEBUG_GROUP_N = 8       # include/migym.h mg_debug_artic_groups
 MG_LAYOUT_HEAD_N, MG_LAYOUT_GROUP_N, MG_LAYOUT_ENVGROUP_N = 13, 14, 5
 # mg_last_rigid_form (include/migym.h): bits of the last single-shape free-body launch
 MG_RIGID_FORM_WIDE, MG_RIGID_FORM_REC, MG_RIGID_FORM_BOX = 1, 2, 4
+# mg_debug_step_builds (include/migym.h): MG_KERNEL_* by value, ints per row
+MG_KERNEL_NAMES = (None, "k_rigid_step1", "k_rigid_step", "k_artic_chain", "k_artic_chain_q", "k_artic_lanes",
+                   "k_env_step", "k_pile_step")
+MG_STEP_BUILD_N = 3
 MG_ATMPL_I_N = 4
 MG_ACOLL_N = 4
 
@@ -205,6 +209,7 @@ def _load():
         "mg_step_time_stats": (i32, [vp, i32, vp, vp, vp]),
         "mg_num_free_bodies": (i32, [vp]),
         "mg_last_rigid_form": (i32, [vp]),
+        "mg_debug_step_builds": (i32, [vp, vp, i32]),
         "mg_debug_rcp_pairs": (i32, [vp, vp, i32]),
         "mg_num_articulations": (i32, [vp]),
         "mg_num_coupled_envs": (i32, [vp]),
@@ -246,7 +251,7 @@ def _load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.mg_abi_version() != 1:
+    if lib.mg_abi_version() != 2:
         raise ImportError("libmigym.so ABI version mismatch")
     return lib
 
@@ -273,7 +278,7 @@ EXPORTED_SYMBOLS = (
     "mg_joint_friction_stats",
     "mg_capacity_stats", "mg_capacity_env_flags", "mg_capacity_tracked",
     "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
-    "mg_last_rigid_form", "mg_debug_rcp_pairs",
+    "mg_last_rigid_form", "mg_debug_step_builds", "mg_debug_rcp_pairs",
 )
 
 

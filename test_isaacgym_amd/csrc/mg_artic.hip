@@ -235,7 +235,3 @@ hipError_t mg_launch_jacobian(const MgArticArgs& A, float* jac, float* mm, hipSt
         hipLaunchKernelGGL(k_artic_jac_mm_g<32>, dim3((A.na + 1) / 2), dim3(64), 0, s, A, jac, mm);
     return hipGetLastError();
 }
-
-hipError_t mg_launch_artic_step(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
-    return mg_launch_artic_lanes(P, A, s);
-}

@@ -252,9 +252,6 @@ __device__ __forceinline__ void chain_solve(const float (&M)[D][D], const float*
     }
 }
 
-#ifndef MG_CHAIN_AFF
-#define MG_CHAIN_AFF 1
-#endif
 // instance a's first body, first DOF and link stride: computed for the
 // blocked layout (AA.aff: no dependent load ahead of the state loads), else
 // its artic_i row
@@ -1045,21 +1042,19 @@ __global__ void __launch_bounds__(64, MG_CHAIN_WAVES) k_artic_chain(MgStep P, Mg
 
 }  // namespace
 
-// serial chains of 2..4 links (fixed base, link l driven by DOF l - 1)
-hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
+// serial chains of 2..4 links (fixed base, link l driven by DOF l - 1): four lanes
+// per chain (k_artic_chain_q) or one, as the build says
+hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, const MgBuild& b, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
-    if (!A.chain || A.nl < 2 || A.nl > 4) return hipErrorNotSupported;
-    // the computed-row form when the upload found the rows affine (and the
-    // fused refresh's rows too, when it writes them); the DOF-force builds only
-    // when the sim reports DOF forces (A.dof_frc)
-    const bool aff = MG_CHAIN_AFF && A.aff && ((A.out_rb == nullptr && A.out_root == nullptr) || A.out_aff);
-    const MgChainForm c = mg_chain_form(A.na, A.ext, A.uni, aff, A.dof_frc);
-    const bool ok = mg_with_int<2, 3, 4>(A.nl, [&](auto nl) {
+    if (!mg_build_fits(b, mg_args_have(A), MG_K_ARTIC_CHAIN, MG_K_ARTIC_CHAIN_Q) || b.size != A.nl || b.aff != (A.aff != 0) ||
+        b.out_aff != (A.out_aff != 0))
+        return hipErrorInvalidValue;
+    const bool ok = mg_with_int<2, 3, 4>(b.size, [&](auto nl) {
         constexpr int NL = decltype(nl)::value;
-        if (c.quad)   // four lanes per chain
-            return MG_LAUNCH_FORM(CF_BITS, c.f, k_artic_chain_q_built(NL, F), (k_artic_chain_q<NL, F>),
+        if (b.kernel == MG_K_ARTIC_CHAIN_Q)
+            return MG_LAUNCH_FORM(CF_BITS, b.form, k_artic_chain_q_built(NL, F), (k_artic_chain_q<NL, F>),
                                   dim3((A.na * 4 + 63) / 64), 0, s, P, A);
-        return MG_LAUNCH_FORM(CF_BITS, c.f, k_artic_chain_built(NL, F), (k_artic_chain<NL, F>),
+        return MG_LAUNCH_FORM(CF_BITS, b.form, k_artic_chain_built(NL, F), (k_artic_chain<NL, F>),
                               dim3((A.na + 63) / 64), 0, s, P, A);
     });
     return ok ? hipGetLastError() : hipErrorNotSupported;

@@ -12,31 +12,19 @@ extern "C" int mg_debug_env_phase_reset(void) {
 }
 #endif
 
-hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s) {
+hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, const MgBuild& b, hipStream_t s) {
     if (A.na <= 0) return hipSuccess;
-    if (!A.fixed_base || A.nl > MG_MAX_LINKS || A.ndof > MG_ENV_SLOTS_WIDE) return hipErrorNotSupported;
-    // instances that hold a friction DOF or own an attractor (migym_capi.cpp lists them apart) step
-    // here, also of a group that steps in k_artic_chain otherwise
-    if (A.jfr && (A.attr_idx || !A.dof_frc)) return hipErrorNotSupported;
-    if (!A.jfr && !A.attr_idx && A.chain && A.nl >= 2 && A.nl <= 4)   // serial chain, one DOF per moving link
-        return mg_launch_artic_chain(P, A, s);
-    const MgSizedForm k = k_artic_lanes_form(A.nl, A.ndof, A.attr_idx, A.dof_frc, A.jfr);
-    const hipError_t e = k_artic_lanes_object(k.f) == MG_ENV_OBJ_JFR ? mg_launch_artic_lanes_jfr(k.maxl, k.f, s, P, A)
-                                                                     : artic_lanes_launch<MG_ENV_OBJ_MAIN>(k.maxl, k.f, s, P, A);
+    if (!mg_build_fits(b, mg_args_have(A), MG_K_ARTIC_LANES)) return hipErrorInvalidValue;
+    const hipError_t e = k_artic_lanes_object(b.form) == MG_ENV_OBJ_JFR ? mg_launch_artic_lanes_jfr(b, s, P, A)
+                                                                        : artic_lanes_launch<MG_ENV_OBJ_MAIN>(b, s, P, A);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s) {
+hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, const MgBuild& b, hipStream_t s) {
     if (A.ne <= 0) return hipSuccess;
-    // velocity slots: DOFs, the floating root's 6, 6 per free body (at most MG_ENV_MAXF)
-    const int slots = A.ndof + (A.floating ? 6 : 0) + 6 * A.max_free;
-    if (A.nl > MG_MAX_LINKS || slots > MG_ENV_SLOTS_WIDE) return hipErrorNotSupported;
-    const MgSizedForm k = k_env_step_form(A.nl, A.ndof, A.floating, slots, A.attr_idx, A.dof_frc, A.ctorque, A.crep, A.jfr);
-    const MgEnvObject obj = k_env_step_object(k.f);
-    // per substep: the narrow phase (one env per wavefront), then the step. The narrow phase's size follows
-    // the env alone (an attractor's 16-link step after k_env_np<4>: tests/test_attractor_gpu.py)
-    const bool wide = mg_env_wide(A.nl, slots);
-    const bool small = A.nl <= 4 && A.ndof <= 4 && !A.floating;
+    if (!mg_build_fits(b, mg_args_have(A), MG_K_ENV_STEP)) return hipErrorInvalidValue;
+    const MgEnvObject obj = k_env_step_object(b.form);
+    // per substep: the narrow phase (one env per wavefront), then the step
     const int np_blocks = (A.ne + 64 / MG_NP_GN - 1) / (64 / MG_NP_GN);
     MgEnvArgs B = A;
     // k_env_np's LDS copy of the scene's shapes, shape boxes and hulls (B.nhull = -1: too large, read from global memory)
@@ -51,13 +39,14 @@ hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s
     for (int sub = 0; sub < P.substeps; ++sub) {
         B.sub = sub;
         B.last = sub == P.substeps - 1 ? 1 : 0;
-        if (wide) MG_LAUNCH((k_env_np<MG_MAX_LINKS, 64, 64>), dim3(A.ne), dim3(64), scene, s, P, B);
-        else if (small) MG_LAUNCH((k_env_np<4, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
-        else MG_LAUNCH((k_env_np<16, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
-        const hipError_t e = obj == MG_ENV_OBJ_JFR    ? mg_launch_env_step_jfr(k.maxl, k.f, s, P, B)
-                             : obj == MG_ENV_OBJ_CREP ? mg_launch_env_step_crep(k.maxl, k.f, s, P, B)
-                             : obj == MG_ENV_OBJ_SENS ? mg_launch_env_step_sens(k.maxl, k.f, s, P, B)
-                                                      : env_step_launch<MG_ENV_OBJ_MAIN>(k.maxl, k.f, s, P, B);
+        if (b.np == 32) MG_LAUNCH((k_env_np<MG_MAX_LINKS, 64, 64>), dim3(A.ne), dim3(64), scene, s, P, B);
+        else if (b.np == 4) MG_LAUNCH((k_env_np<4, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
+        else if (b.np == 16) MG_LAUNCH((k_env_np<16, G16, MG_NP_GN>), dim3(np_blocks), dim3(64), scene, s, P, B);
+        else return hipErrorInvalidValue;
+        const hipError_t e = obj == MG_ENV_OBJ_JFR    ? mg_launch_env_step_jfr(b, s, P, B)
+                             : obj == MG_ENV_OBJ_CREP ? mg_launch_env_step_crep(b, s, P, B)
+                             : obj == MG_ENV_OBJ_SENS ? mg_launch_env_step_sens(b, s, P, B)
+                                                      : env_step_launch<MG_ENV_OBJ_MAIN>(b, s, P, B);
         if (e != hipSuccess) return e;
     }
     return hipGetLastError();

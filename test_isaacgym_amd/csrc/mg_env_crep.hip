@@ -2,6 +2,6 @@
 // contact torque row (the rigid contact list).
 #include "mg_env_kernels.h"
 
-hipError_t mg_launch_env_step_crep(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    return env_step_launch<MG_ENV_OBJ_CREP>(maxl, form, s, P, A);
+hipError_t mg_launch_env_step_crep(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    return env_step_launch<MG_ENV_OBJ_CREP>(b, s, P, A);
 }

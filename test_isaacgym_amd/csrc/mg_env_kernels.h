@@ -2539,23 +2539,24 @@ __global__ void __launch_bounds__(64) k_artic_lanes(MgStep P, MgArticArgs AA) {
 
 static_assert(MG_MAX_LINKS == 32 && MG_ENV_G == 16, "the sizes mg_forms.h lists");
 
-// Launches the (maxl, form) build of k_env_step / k_artic_lanes if it is one
-// of object OBJ's (so each object compiles its own forms and no other); 16
-// lanes per env: 4 envs per block, 64: one.
+// Launches build b of k_env_step / k_artic_lanes if it is one of object OBJ's
+// (so each object compiles its own forms and no other; mg_launch_env_step and
+// mg_launch_artic_lanes have checked it against the block); 16 lanes per env:
+// 4 envs per block, 64: one.
 template <MgEnvObject OBJ>
-hipError_t env_step_launch(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    const bool ok = mg_with_int<32, 16, 4>(maxl, [&](auto maxl_) {
+hipError_t env_step_launch(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    const bool ok = mg_with_int<32, 16, 4>(b.size, [&](auto maxl_) {
         constexpr int MAXL = decltype(maxl_)::value, G = mg_env_lanes(MAXL);
-        return MG_LAUNCH_FORM(EF_BITS, form, k_env_step_built(MAXL, G, F) && k_env_step_object(F) == OBJ,
+        return MG_LAUNCH_FORM(EF_BITS, b.form, k_env_step_built(MAXL, G, F) && k_env_step_object(F) == OBJ,
                               (k_env_step<MAXL, G, F>), dim3((A.ne + 64 / G - 1) / (64 / G)), 0, s, P, A);
     });
     return ok ? hipSuccess : hipErrorNotSupported;
 }
 template <MgEnvObject OBJ>
-hipError_t artic_lanes_launch(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgArticArgs& A) {
-    const bool ok = mg_with_int<32, 16, 4>(maxl, [&](auto maxl_) {
+hipError_t artic_lanes_launch(const MgBuild& b, hipStream_t s, const MgStep& P, const MgArticArgs& A) {
+    const bool ok = mg_with_int<32, 16, 4>(b.size, [&](auto maxl_) {
         constexpr int MAXL = decltype(maxl_)::value, G = mg_env_lanes(MAXL);
-        return MG_LAUNCH_FORM(LF_BITS, form, k_artic_lanes_built(MAXL, G, F) && k_artic_lanes_object(F) == OBJ,
+        return MG_LAUNCH_FORM(LF_BITS, b.form, k_artic_lanes_built(MAXL, G, F) && k_artic_lanes_object(F) == OBJ,
                               (k_artic_lanes<MAXL, G, F>), dim3((A.na + 64 / G - 1) / (64 / G)), 0, s, P, A);
     });
     return ok ? hipSuccess : hipErrorNotSupported;

@@ -2,6 +2,6 @@
 // DESIGN.md §3.13). An object of their own so that the library builds in parallel.
 #include "mg_env_kernels.h"
 
-hipError_t mg_launch_env_step_sens(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
-    return env_step_launch<MG_ENV_OBJ_SENS>(maxl, form, s, P, A);
+hipError_t mg_launch_env_step_sens(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A) {
+    return env_step_launch<MG_ENV_OBJ_SENS>(b, s, P, A);
 }

@@ -2,7 +2,11 @@
 // no device header (tests/step_forms_check.cpp includes it alone). A step kernel's bool template
 // parameters are the bits of one form word F; per kernel this header holds the bits,
 // <kernel>_built (the single list of the builds that exist: the kernel static_asserts it, the
-// launcher instantiates nothing else) and <kernel>_form (a launch's form from plain inputs).
+// launcher instantiates nothing else) and <kernel>_form (a form from plain inputs). The _form
+// functions are internals of the choosers at the end of the file: one chooser per kernel family
+// states "this launch runs this kernel at this form" (MgBuild). The route refuses by it
+// (mg_route.h), the argument builders fill the pointers it needs (migym_capi.cpp), the launchers
+// launch it. Nothing else calls a _form function or picks a kernel.
 #pragma once
 #include <stddef.h>
 #include <type_traits>
@@ -144,3 +148,160 @@ constexpr MgSizedForm k_artic_lanes_form(int nl, int ndof, bool attr_idx, bool d
 enum : unsigned { PF_CREP = 1, PF_BITS = 1 };
 constexpr bool k_pile_step_built(unsigned f) { return !(f >> PF_BITS); }
 constexpr unsigned k_pile_step_form(bool crep) { return crep ? PF_CREP : 0; }
+
+// ---- the choosers: which kernel, at which size and form, a launch runs ----
+// what only a simulate knows: the +Z ground basis, an applied wrench is pending, the step writes
+// refreshed rows (the fused refresh or the host stage), the device's compute units
+struct MgRun { bool upz, ext, step_out; int cus; };
+constexpr bool mg_step_is_upz(const float n[3], const float t1[3], const float t2[3]) {
+    return n[0] == 0.0f && n[1] == 0.0f && n[2] == 1.0f && t1[0] == 0.0f && t1[1] == 1.0f && t1[2] == 0.0f &&
+           t2[0] == -1.0f && t2[1] == 0.0f && t2[2] == 0.0f;
+}
+// the launches' size limits (mg_internal.h asserts them equal to MG_MAX_LINKS, MG_ENV_SLOTS_WIDE, MG_MAX_CONTACTS)
+enum { MG_FORM_MAX_LINKS = 32, MG_FORM_SLOTS_WIDE = 32, MG_FORM_MAX_CONTACTS = 8 };
+#ifndef MG_CHAIN_AFF
+#define MG_CHAIN_AFF 1
+#endif
+
+// the kernel ids (mg_debug_step_builds reports them: include/migym.h MG_KERNEL_*)
+enum MgKernel {
+    MG_K_NONE = 0, MG_K_RIGID_STEP1 = MG_KERNEL_RIGID_STEP1, MG_K_RIGID_STEP = MG_KERNEL_RIGID_STEP,
+    MG_K_ARTIC_CHAIN = MG_KERNEL_ARTIC_CHAIN, MG_K_ARTIC_CHAIN_Q = MG_KERNEL_ARTIC_CHAIN_Q,
+    MG_K_ARTIC_LANES = MG_KERNEL_ARTIC_LANES, MG_K_ENV_STEP = MG_KERNEL_ENV_STEP, MG_K_PILE_STEP = MG_KERNEL_PILE_STEP
+};
+// kernel<size, form>: size is NL (the chains), MAXL in mg_env_lanes(MAXL) lanes (k_env_step,
+// k_artic_lanes), MAXC (k_rigid_step), else 0. np: k_env_step's narrow phase k_env_np<4 | 16 | 32>.
+// aff, out_aff: MgArticArgs' values of the chains (rows, refreshed rows computed, not loaded).
+// kernel MG_K_NONE: the launch has no such part (a free-body half without bodies); built false: no such build.
+struct MgBuild {
+    int kernel = MG_K_NONE, size = 0;
+    unsigned form = 0;
+    int np = 0;
+    bool aff = false, out_aff = false;
+    bool built = false;
+};
+// the free bodies' two launches: single-shape bodies (k_rigid_step1), then the others (k_rigid_step)
+struct MgBuilds {
+    MgBuild one, multi;
+    constexpr bool built() const { return (one.kernel || multi.kernel) && (!one.kernel || one.built) && (!multi.kernel || multi.built); }
+};
+
+// the routed features a build carries (EF_* by value: mg_route.h's RT_*)
+constexpr unsigned mg_build_carried(const MgBuild& b) {
+    const unsigned f = b.form;
+    switch (b.kernel) {
+        case MG_K_RIGID_STEP1:
+        case MG_K_RIGID_STEP: return (f & RF_ATTR ? EF_ATTR : 0) | (f & RF_CREP ? EF_CREP : 0);
+        case MG_K_ARTIC_CHAIN:
+        case MG_K_ARTIC_CHAIN_Q: return f & CF_FRC ? EF_FRC : 0;
+        case MG_K_ARTIC_LANES: return (f & LF_ATTR ? EF_ATTR : 0) | (f & LF_FRC ? EF_FRC : 0) | (f & LF_JFR ? EF_JFR : 0);
+        case MG_K_ENV_STEP: return f;
+        case MG_K_PILE_STEP: return f & PF_CREP ? EF_CREP : 0;
+        default: return 0;
+    }
+}
+constexpr unsigned mg_build_carried(const MgBuilds& b) {
+    return (b.one.kernel ? mg_build_carried(b.one) : ~0u) & (b.multi.kernel ? mg_build_carried(b.multi) : ~0u) &
+           (b.one.kernel || b.multi.kernel ? ~0u : 0u);
+}
+
+// The optional members of its argument block a build's kernel dereferences unconditionally:
+// attr_idx and attr; dof_frc; ctorque; crep, crep_n and crep_body; uni; slot_rec; ext (the chains'
+// EXT forms: the other kernels test ext themselves). The builders fill exactly these, the
+// launchers launch nothing that lacks one.
+enum : unsigned { MG_NEED_ATTR = 1, MG_NEED_DOF_FRC = 2, MG_NEED_CTORQUE = 4, MG_NEED_CREP = 8, MG_NEED_UNI = 16,
+                  MG_NEED_SLOT_REC = 32, MG_NEED_EXT = 64 };
+constexpr unsigned mg_build_needs(const MgBuild& b) {
+    const unsigned f = b.form;
+    switch (b.kernel) {
+        case MG_K_RIGID_STEP1:
+            return (f & RF_ATTR ? MG_NEED_ATTR : 0) | (f & RF_CREP ? MG_NEED_CREP : 0) | (f & RF_REC ? MG_NEED_SLOT_REC : 0);
+        case MG_K_RIGID_STEP: return (f & RF_ATTR ? MG_NEED_ATTR : 0) | (f & RF_CREP ? MG_NEED_CREP : 0);
+        case MG_K_ARTIC_CHAIN:
+        case MG_K_ARTIC_CHAIN_Q:
+            return (f & CF_EXT ? MG_NEED_EXT : 0) | (f & CF_UNI ? MG_NEED_UNI : 0) | (f & CF_FRC ? MG_NEED_DOF_FRC : 0);
+        case MG_K_ARTIC_LANES: return (f & LF_ATTR ? MG_NEED_ATTR : 0) | (f & LF_FRC ? MG_NEED_DOF_FRC : 0);
+        case MG_K_ENV_STEP:
+            return (f & EF_ATTR ? MG_NEED_ATTR : 0) | (f & EF_FRC ? MG_NEED_DOF_FRC : 0) | (f & EF_SENS ? MG_NEED_CTORQUE : 0) |
+                   (f & EF_CREP ? MG_NEED_CREP : 0);
+        case MG_K_PILE_STEP: return f & PF_CREP ? MG_NEED_CREP : 0;
+        default: return 0;
+    }
+}
+// a launcher's host check: `b` is a build of `kernel` (or of `kernel2`) and `have`, the MG_NEED_* of the
+// block's members that are set, holds all it needs
+constexpr bool mg_build_fits(const MgBuild& b, unsigned have, int kernel, int kernel2 = MG_K_NONE) {
+    return b.built && (b.kernel == kernel || (kernel2 && b.kernel == kernel2)) && !(mg_build_needs(b) & ~have);
+}
+
+// An uncoupled articulation group's launch of `count` instances. A serial chain of 2 to 4 links
+// without attractor and joint friction steps in the chain kernels (four lanes per chain up to
+// MG_CHAIN_QUAD_MAX lanes), everything else in k_artic_lanes. uni: the group's shared constants
+// (chains only). aff, out_aff: the group's rows / refreshed rows are affine; a split launch loads
+// them. The computed-row form needs the refreshed rows computed too when the step writes them.
+constexpr MgBuild mg_choose_artic(int nl, int ndof, bool fixed_base, bool chain, bool uni_mass, bool aff, bool out_aff,
+                                  bool split, int count, unsigned feat, const MgRun& run) {
+    MgBuild b;
+    const bool attr = feat & EF_ATTR, frc = feat & EF_FRC, jfr = feat & EF_JFR;
+    if (!jfr && !attr && chain && nl >= 2 && nl <= 4) {   // serial chain, one DOF per moving link
+        b.aff = !split && aff;
+        b.out_aff = !split && out_aff;
+        const MgChainForm c = mg_chain_form(count, run.ext, uni_mass, MG_CHAIN_AFF && b.aff && (!run.step_out || b.out_aff), frc);
+        b.kernel = c.quad ? MG_K_ARTIC_CHAIN_Q : MG_K_ARTIC_CHAIN;
+        b.size = nl;
+        b.form = c.f;
+        b.built = c.quad ? k_artic_chain_q_built(nl, c.f) : k_artic_chain_built(nl, c.f);
+        return b;
+    }
+    const MgSizedForm k = k_artic_lanes_form(nl, ndof, attr, frc, jfr);
+    b.kernel = MG_K_ARTIC_LANES;
+    b.size = k.maxl;
+    b.form = k.f;
+    b.built = fixed_base && nl <= MG_FORM_MAX_LINKS && ndof <= MG_FORM_SLOTS_WIDE && k_artic_lanes_built(k.maxl, mg_env_lanes(k.maxl), k.f);
+    return b;
+}
+
+// A coupled group's launch: nl, ndof, floating of its articulation template (0: none), max_free free
+// bodies per env. Velocity slots: DOFs, the floating root's 6, 6 per free body. The narrow phase's
+// size follows the env alone (an attractor's 16-link step runs after k_env_np<4>).
+constexpr MgBuild mg_choose_env(int nl, int ndof, bool floating, int max_free, unsigned feat, const MgRun&) {
+    MgBuild b;
+    const int slots = ndof + (floating ? 6 : 0) + 6 * max_free;
+    const MgSizedForm k = k_env_step_form(nl, ndof, floating, slots, feat & EF_ATTR, feat & EF_FRC, feat & EF_SENS,
+                                          feat & EF_CREP, feat & EF_JFR);
+    b.kernel = MG_K_ENV_STEP;
+    b.size = k.maxl;
+    b.form = k.f;
+    b.np = mg_env_wide(nl, slots) ? 32 : nl <= 4 && ndof <= 4 && !floating ? 4 : 16;
+    b.built = nl <= MG_FORM_MAX_LINKS && slots <= MG_FORM_SLOTS_WIDE && k_env_step_built(k.maxl, mg_env_lanes(k.maxl), k.f);
+    return b;
+}
+
+constexpr MgBuild mg_choose_pile(unsigned feat, const MgRun&) {
+    MgBuild b;
+    b.kernel = MG_K_PILE_STEP;
+    b.form = k_pile_step_form(feat & EF_CREP);
+    b.built = k_pile_step_built(b.form);
+    return b;
+}
+
+// The free bodies: nf1 single-shape ones in blocks of 64, then nf - nf1 others. lds_bytes: the
+// template records'; slot_rec: the layout holds the packed slot record (a reporting launch reads
+// the slot's indices from their arrays instead); box_only: MgLayout::free_flags[0].
+constexpr MgBuilds mg_choose_free(int nf1, int nf, size_t lds_bytes, bool slot_rec, bool box_only, unsigned feat,
+                                  const MgRun& run) {
+    MgBuilds b;
+    const bool attr = feat & EF_ATTR, crep = feat & EF_CREP;
+    if (nf1 > 0) {
+        b.one.kernel = MG_K_RIGID_STEP1;
+        b.one.form = k_rigid_step1_form(run.upz, (nf1 + 63) / 64, run.cus, lds_bytes, slot_rec && !crep, attr, crep, false, box_only);
+        b.one.built = k_rigid_step1_built(b.one.form);
+    }
+    if (nf > nf1) {
+        b.multi.kernel = MG_K_RIGID_STEP;
+        b.multi.size = MG_FORM_MAX_CONTACTS;
+        b.multi.form = k_rigid_step_form(run.upz, attr, crep);
+        b.multi.built = k_rigid_step_built(b.multi.form, b.multi.size, true);
+    }
+    return b;
+}

@@ -488,26 +488,48 @@ extern thread_local MgKernelTimer* mg_timer;
 // launchers (defined in the .hip files)
 hipError_t mg_launch_render(const MgRenderArgs& A, int nblocks, hipStream_t s);
 hipError_t mg_launch_cube_pick(const mg_cube_pick_args& A, hipStream_t s);
-hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, hipStream_t s);
-// the k_env_step<maxl, .., form> / k_artic_lanes builds of the other objects (mg_forms.h
-// k_env_step_object: contact moments, reporting, joint friction); hipErrorNotSupported: not one of its builds
-hipError_t mg_launch_env_step_sens(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
-hipError_t mg_launch_env_step_crep(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
-hipError_t mg_launch_env_step_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
-hipError_t mg_launch_artic_lanes_jfr(int maxl, unsigned form, hipStream_t s, const MgStep& P, const MgArticArgs& A);
+
+// The step launchers launch the build they are handed (mg_forms.h MgBuild: mg_simulate asks the
+// route for it) and choose nothing. Before anything is launched each checks on the host that the
+// build is one of its kernel's and that the block holds every member that build dereferences
+// (mg_build_fits), else hipErrorInvalidValue; hipErrorNotSupported: no such build in this library.
+static_assert(MG_FORM_MAX_LINKS == MG_MAX_LINKS && MG_FORM_SLOTS_WIDE == MG_ENV_SLOTS_WIDE &&
+                  MG_FORM_MAX_CONTACTS == MG_MAX_CONTACTS, "the sizes mg_forms.h lists");
+// the MG_NEED_* members of a block that are set
+inline unsigned mg_args_have(const MgRigidArgs& A) {
+    return (A.attr_idx && A.attr ? MG_NEED_ATTR : 0) | (A.crep && A.crep_n && A.crep_body ? MG_NEED_CREP : 0) |
+           (A.slot_rec ? MG_NEED_SLOT_REC : 0) | (A.ext ? MG_NEED_EXT : 0);
+}
+inline unsigned mg_args_have(const MgArticArgs& A) {
+    return (A.attr_idx && A.attr ? MG_NEED_ATTR : 0) | (A.dof_frc ? MG_NEED_DOF_FRC : 0) | (A.uni ? MG_NEED_UNI : 0) |
+           (A.ext ? MG_NEED_EXT : 0);
+}
+inline unsigned mg_args_have(const MgEnvArgs& A) {
+    return (A.attr_idx && A.attr ? MG_NEED_ATTR : 0) | (A.dof_frc ? MG_NEED_DOF_FRC : 0) | (A.ctorque ? MG_NEED_CTORQUE : 0) |
+           (A.crep && A.crep_n && A.crep_body ? MG_NEED_CREP : 0) | (A.ext ? MG_NEED_EXT : 0);
+}
+inline unsigned mg_args_have(const MgPileArgs& A) {
+    return (A.crep && A.crep_n && A.crep_body ? MG_NEED_CREP : 0) | (A.ext ? MG_NEED_EXT : 0);
+}
+hipError_t mg_launch_env_step(const MgStep& P, const MgEnvArgs& A, const MgBuild& b, hipStream_t s);
+// the k_env_step / k_artic_lanes builds of the other objects (mg_forms.h k_env_step_object: contact
+// moments, reporting, joint friction); hipErrorNotSupported: not one of its builds
+hipError_t mg_launch_env_step_sens(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_env_step_crep(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_env_step_jfr(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
+hipError_t mg_launch_artic_lanes_jfr(const MgBuild& b, hipStream_t s, const MgStep& P, const MgArticArgs& A);
 hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
-hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s);
+hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, const MgBuild& b, hipStream_t s);
 extern "C" int mg_env_carry_floats(void);   // per-env record sizes of the coupled step (mg_env.hip)
 extern "C" int mg_env_ctab_floats(void);
 int mg_env_ctab_record_floats(int wide);   // one env's contact table in a 16- / 64-lane group
-// form (optional): the MG_RIGID_FORM_* bits of the single-shape launch, -1 when there was none
-hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s, int* form = nullptr);
+// b.one steps the single-shape bodies (the first A.nf1 slots), b.multi the others
+hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, const MgBuilds& b, hipStream_t s);
 // rcp2_ieee (mg_pair.h) over n floats of device memory (mg_debug_rcp_pairs)
 hipError_t mg_launch_rcp_pairs(const float* d, float* out, int n, hipStream_t s);
-hipError_t mg_launch_artic_step(const MgStep& P, const MgArticArgs& A, hipStream_t s);
-hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, hipStream_t s);
-hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, hipStream_t s);
+hipError_t mg_launch_artic_lanes(const MgStep& P, const MgArticArgs& A, const MgBuild& b, hipStream_t s);
+hipError_t mg_launch_artic_chain(const MgStep& P, const MgArticArgs& A, const MgBuild& b, hipStream_t s);
 hipError_t mg_launch_gather_rows(const float* soa, int stride, int ncol, const int* ids, int n,
                                  float* aos, hipStream_t s);
 hipError_t mg_launch_gather_rb_root(const float* soa, int stride, int ncol, const int* perm, int nb, float* rb,

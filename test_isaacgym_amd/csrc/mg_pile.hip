@@ -698,9 +698,10 @@ __global__ void __launch_bounds__(64) k_pile_step(MgStep P, MgPileArgs A) {
 
 }  // namespace
 
-hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, hipStream_t s) {
+hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, const MgBuild& b, hipStream_t s) {
     if (A.ne <= 0) return hipSuccess;
-    const bool ok = MG_LAUNCH_FORM(PF_BITS, k_pile_step_form(A.crep), k_pile_step_built(F), k_pile_step<F>,
+    if (!mg_build_fits(b, mg_args_have(A), MG_K_PILE_STEP)) return hipErrorInvalidValue;
+    const bool ok = MG_LAUNCH_FORM(PF_BITS, b.form, k_pile_step_built(F), k_pile_step<F>,
                                    dim3(A.ne), 0, s, P, A);
     return ok ? hipGetLastError() : hipErrorNotSupported;
 }

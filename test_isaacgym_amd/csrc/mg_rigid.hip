@@ -1618,36 +1618,17 @@ hipError_t mg_launch_rcp_pairs(const float* d, float* out, int n, hipStream_t s)
     return hipGetLastError();
 }
 
-bool mg_step_is_upz(const MgStep& P) {
-    return P.n[0] == 0.0f && P.n[1] == 0.0f && P.n[2] == 1.0f && P.t1[0] == 0.0f && P.t1[1] == 1.0f &&
-           P.t1[2] == 0.0f && P.t2[0] == -1.0f && P.t2[1] == 0.0f && P.t2[2] == 0.0f;
-}
-
-static int mg_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] <= 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
 // A.free_ids lists the single-shape bodies first (A.nf1 of them), then the
-// multi-shape ones; each group is its own launch.
-hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream_t s, int* form) {
-    if (form) *form = -1;
+// multi-shape ones; each group is its own launch, of the build b holds for it
+// (mg_forms.h mg_choose_free: the slot record goes to the one-round builds that read it).
+hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, const MgBuilds& b, hipStream_t s) {
     if (A.nf <= 0) return hipSuccess;
-    const bool upz = mg_step_is_upz(P);
     MgRigidArgs A1 = A, A2 = A;
     A2.root_src = nullptr;   // fused root sets only with single-shape bodies (migym_capi.cpp)
     A2.out_rb = nullptr;     // so is the fused refresh (MG_FUSE_STEP_OUT)
     A2.out_root = nullptr;
     A2.gpatch = nullptr;     // ground patches: single-shape bodies (multi-shape ones keep per-point rows)
     A2.slot_rec = nullptr;   // the packed slot record: one-round single-shape launches by slot only
-    if (A.free_ids) A1.slot_rec = nullptr;
     A1.nf = A.nf1;
     A2.nf = A.nf - A.nf1;
     if (A.free_ids) {
@@ -1663,8 +1644,9 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         A2.crep_n = A.crep_n ? A.crep_n + A.nf1 : nullptr;
         A2.crep_body = A.crep_body ? A.crep_body + A.nf1 : nullptr;
     }
-    // which builds run: mg_forms.h (k_rigid_step1_form, k_rigid_step_form)
-    if (A.crep) A1.slot_rec = nullptr;
+    if ((A1.nf > 0 && !mg_build_fits(b.one, mg_args_have(A1), MG_K_RIGID_STEP1)) ||
+        (A2.nf > 0 && !mg_build_fits(b.multi, mg_args_have(A2), MG_K_RIGID_STEP)))
+        return hipErrorInvalidValue;
     bool ok = true;
     if (A1.nf > 0) {
         // a wide launch is issue-bound, not latency-bound: it dispatches
@@ -1674,17 +1656,13 @@ hipError_t mg_launch_rigid_step(const MgStep& P, const MgRigidArgs& A, hipStream
         // slots of two scalar ones when waves share it: DESIGN.md §3.2).
         const int blocks = (A1.nf + 63) / 64;
         const size_t lds = (size_t)A.ntb * MG_TREC_N * sizeof(float);
-        const unsigned f = k_rigid_step1_form(upz, blocks, mg_cu_count(), lds, A.slot_rec, A.attr_idx, A.crep,
-                                              A.free_ids, A.box_only);
-        if (form) *form = mg_rigid_form_public(f);
-        ok = MG_LAUNCH_FORM(RF_BITS, f, k_rigid_step1_built(F), k_rigid_step1<F>, dim3(blocks), (F & RF_LDS) ? lds : 0,
-                            s, P, A1);
+        ok = MG_LAUNCH_FORM(RF_BITS, b.one.form, k_rigid_step1_built(F), k_rigid_step1<F>, dim3(blocks),
+                            (F & RF_LDS) ? lds : 0, s, P, A1);
     }
     if (A2.nf > 0) {
         const int blocks = (A2.nf + 63) / 64;
-        ok = MG_LAUNCH_FORM(RF_BITS, k_rigid_step_form(upz, A.attr_idx, A.crep),
-                            k_rigid_step_built(F, MG_MAX_CONTACTS, true), (k_rigid_step<F, MG_MAX_CONTACTS, true>),
-                            dim3(blocks), 0, s, P, A2) && ok;
+        ok = MG_LAUNCH_FORM(RF_BITS, b.multi.form, k_rigid_step_built(F, MG_MAX_CONTACTS, true),
+                            (k_rigid_step<F, MG_MAX_CONTACTS, true>), dim3(blocks), 0, s, P, A2) && ok;
     }
     return ok ? hipGetLastError() : hipErrorNotSupported;
 }

@@ -8,12 +8,15 @@
 // buffers (migym_capi.cpp); mg_simulate reports the route's refusal, then walks its launches.
 //
 // Of MgLayout it reads: nb, nd, nf1, nf_rigid, n_pile, step_out_ok; perm; artic_step; groups (chain, uni_mass,
-// nl, ndof, aff, step_offset, step_count); env_groups (tmpl, nl, ndof, floating, max_free, offset,
-// count); body_class, body_grp, body_inst, body_artic, artic_info, env_d0, actor_dof, atmpl, link_i.
+// nl, ndof, fixed_base, aff, out_aff, step_offset, step_count); env_groups (tmpl, nl, ndof, floating,
+// max_free, offset, count); trec, slot_rec, free_flags (their sizes, free_flags[0]); body_class, body_grp,
+// body_inst, body_artic, artic_info, env_d0, actor_dof, atmpl, link_i.
 //
 // The next feature: one RT_* bit, one routing term in mg_plan_route (which launches get the bit),
-// and one entry in the alphabet of tests/step_route_check.cpp. Whether a launch that carries it
-// has a build is not written here: mg_route_carried asks mg_forms.h.
+// one term in its family's chooser in mg_forms.h (which build carries it, which pointer that build
+// needs), and one entry in the alphabet of tests/step_route_check.cpp. Which kernel and form a
+// launch runs is not written here: mg_route_builds asks the chooser, for the refusals below and
+// for mg_simulate alike.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -107,38 +110,35 @@ inline int mg_route_msg(std::string& out, int code, const char* fmt, ...) {
     return code;
 }
 
-// The features carried by the build a launcher chooses for `l` (the _form calls of mg_launch_artic_lanes,
-// mg_launch_env_step, mg_launch_pile_step, mg_launch_rigid_step); built: that build exists
-inline unsigned mg_route_carried(const MgLayout& L, const MgLaunch& l, bool& built) {
-    const bool attr = l.feat & RT_ATTR, frc = l.feat & RT_FRC, sens = l.feat & RT_SENS, crep = l.feat & RT_CREP, jfr = l.feat & RT_JFR;
+// The build(s) launch `l` runs under `run`: the group's shape out of the layout, handed to its
+// family's chooser (mg_forms.h). The free bodies' launch has up to two, every other one `one`.
+inline MgBuilds mg_route_builds(const MgLayout& L, const MgLaunch& l, const MgRun& run) {
+    MgBuilds b;
     if (l.family == MG_FAM_ARTIC) {
         const MgArticGroup& g = L.groups[l.group];
-        if (!jfr && !attr && g.chain && g.nl >= 2 && g.nl <= 4) {   // serial chain, one DOF per moving link
-            const MgChainForm c = mg_chain_form(l.count, false, g.uni_mass, !l.split && g.aff, frc);
-            built = c.quad ? k_artic_chain_q_built(g.nl, c.f) : k_artic_chain_built(g.nl, c.f);
-            return c.f & CF_FRC ? RT_FRC : 0;
-        }
-        const MgSizedForm k = k_artic_lanes_form(g.nl, g.ndof, attr, frc, jfr);
-        built = k_artic_lanes_built(k.maxl, mg_env_lanes(k.maxl), k.f);
-        return (k.f & LF_ATTR ? RT_ATTR : 0) | (k.f & LF_FRC ? RT_FRC : 0) | (k.f & LF_JFR ? RT_JFR : 0);
-    }
-    if (l.family == MG_FAM_ENV) {
+        b.one = mg_choose_artic(g.nl, g.ndof, g.fixed_base, g.chain, g.uni_mass, g.aff, g.out_aff, l.split, l.count, l.feat, run);
+    } else if (l.family == MG_FAM_ENV) {
         const MgEnvGroup& g = L.env_groups[l.group];
-        const int nl = g.tmpl >= 0 ? g.nl : 0, ndof = g.tmpl >= 0 ? g.ndof : 0, fl = g.tmpl >= 0 ? g.floating : 0;
-        const MgSizedForm k = k_env_step_form(nl, ndof, fl, ndof + (fl ? 6 : 0) + 6 * g.max_free, attr, frc, sens, crep, jfr);
-        built = k_env_step_built(k.maxl, mg_env_lanes(k.maxl), k.f);
-        return k.f;
+        const bool art = g.tmpl >= 0;
+        b.one = mg_choose_env(art ? g.nl : 0, art ? g.ndof : 0, art && g.floating, g.max_free, l.feat, run);
+    } else if (l.family == MG_FAM_PILE) {
+        b.one = mg_choose_pile(l.feat, run);
+    } else {
+        b = mg_choose_free(L.nf1, L.nf_rigid, L.trec.size() * sizeof(float), !L.slot_rec.empty(),
+                           !L.free_flags.empty() && L.free_flags[0], l.feat, run);
     }
-    if (l.family == MG_FAM_PILE) {
-        const unsigned f = k_pile_step_form(crep);
-        built = k_pile_step_built(f);
-        return f & PF_CREP ? RT_CREP : 0;
-    }
-    // single-shape free bodies, then the others (the forms' other inputs change neither answer)
-    const unsigned f1 = k_rigid_step1_form(true, 1, 1, 0, true, attr, crep, false, false), f2 = k_rigid_step_form(true, attr, crep);
-    built = (L.nf1 == 0 || k_rigid_step1_built(f1)) && (L.nf_rigid == L.nf1 || k_rigid_step_built(f2, 8, true));
-    const unsigned f = (L.nf1 > 0 ? f1 : f2) & (L.nf_rigid > L.nf1 ? f2 : f1);
-    return (f & RF_ATTR ? RT_ATTR : 0) | (f & RF_CREP ? RT_CREP : 0);
+    return b;
+}
+
+// Every MgRun a simulate can form for `l`, in turn: both ground bases, a wrench pending or not,
+// refreshed rows written or not, and a device on each side of k_rigid_step1's wide threshold for
+// the launch's blocks (0 CUs: every launch is wide; one CU per block: none is). fn(run) -> false stops.
+template <class Fn>
+inline bool mg_route_each_run(const MgLayout& L, const MgLaunch& l, Fn&& fn) {
+    const int blocks = l.family == MG_FAM_FREE ? (L.nf1 + 63) / 64 : 0;
+    for (int m = 0; m < 16; ++m)
+        if (!fn(MgRun{(m & 1) != 0, (m & 2) != 0, (m & 4) != 0, m & 8 ? blocks : 0})) return false;
+    return true;
 }
 
 // Plans the route. Returns MG_OK, or a table's validation error with its message in `err` (then
@@ -338,10 +338,15 @@ inline int mg_plan_route(const MgLayout& L, const MgRouteIn& in, MgRoute& R, std
         R.launches.push_back({MG_FAM_FREE, 0, 0, L.nf_rigid, (attr_free ? RT_ATTR : 0u) | (in.crep ? RT_CREP : 0u), false});
 
     // ---- a launch whose build does not exist, or drops a feature routed to it
+    // under any MgRun a simulate can form: the first such run's loss words the refusal
     for (const MgLaunch& l : R.launches) {
-        bool built = false;
-        const unsigned lost = l.feat & ~mg_route_carried(L, l, built);
-        if (built && !lost) continue;
+        unsigned lost = 0;
+        if (mg_route_each_run(L, l, [&](const MgRun& run) {
+                const MgBuilds b = mg_route_builds(L, l, run);
+                lost = l.feat & ~mg_build_carried(b);
+                return b.built() && !lost;
+            }))
+            continue;
         if (l.family == MG_FAM_ARTIC && (l.feat & RT_JFR) && lost == RT_ATTR)
             mg_route_msg(launch_refusal, 0, "actor %d: joint friction (DOF friction > 0) together with an attractor on an "
                          "articulation of the same group is not built", artic_jactor[l.group]);

@@ -328,7 +328,9 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     hipStream_t last_stream = nullptr;
     bool stepped = false;
     bool capturing = false;       // the last simulate was recorded into a graph
-    int rigid_form = -1;          // MG_RIGID_FORM_* bits of the last free-body launch (mg_last_rigid_form)
+    int cus = 256;                // the device's compute units (MgRun::cus), read once at mg_create_sim
+    // the builds the last simulate launched, in launch order (mg_debug_step_builds, mg_last_rigid_form)
+    std::vector<MgBuild> builds;
     // ring of per-simulate event pairs for live kernel timing (bench.py roofline)
     static constexpr int kRing = 256;
     static constexpr int kKern = 8;   // kernels timed per simulate (dispatch timestamps)
@@ -543,6 +545,8 @@ mg_sim* mg_create_sim(int32_t device, const mg_sim_params* params) {
     mg_sim* s = new mg_sim();
     s->device = device;
     s->params = *params;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) s->cus = cus;
     for (int k = 0; k < mg_sim::kRing; ++k) {
         bool ok = hipEventCreate(&s->ring_b[k]) == hipSuccess && hipEventCreate(&s->ring_e[k]) == hipSuccess;
         for (int j = 0; j < mg_sim::kKern && ok; ++j)
@@ -788,20 +792,22 @@ static StepOut step_out(const mg_sim* s, const MgFusion::Step& fs) {
 }
 
 // The argument blocks of the route's launches (mg_route.h). A launch's feature pointers follow
-// its bits and nothing else.
+// its build's form and nothing else: each optional member is set exactly when the build
+// dereferences it (mg_forms.h mg_build_needs), which the launcher checks again.
 // An articulation group's launch: over all its stepped instances, or, in a group with owners
 // (l.split: rows loaded from the split table, not computed), over the plain ones, those that
 // hold a friction DOF or those that own an attractor.
-static MgArticArgs artic_args(mg_sim* s, const MgLaunch& l, const StepOut& O) {
+static MgArticArgs artic_args(mg_sim* s, const MgLaunch& l, const MgBuild& b, const StepOut& O) {
     const MgArticGroup& g = s->layout.groups[l.group];
+    const unsigned need = mg_build_needs(b);
     MgArticArgs A{};
     // the DOF part's validity is a flag in the block (MG_CHAIN_UNI_DOFOK), not
     // a launch choice: a captured launch follows later set_dof_props
-    A.uni = g.uni_mass && !(l.feat & (RT_ATTR | RT_JFR)) ? s->d_chain_uni + (size_t)l.group * MG_CHAIN_UNI_N : nullptr;
+    A.uni = need & MG_NEED_UNI ? s->d_chain_uni + (size_t)l.group * MG_CHAIN_UNI_N : nullptr;
     A.na = l.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
     A.artic_i = (l.split ? s->d_artic_split : s->d_artic_step) + (size_t)l.row0 * MG_ARTIC_I_N;
-    A.aff = l.split ? 0 : g.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
-    A.out_aff = l.split ? 0 : g.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
+    A.aff = b.aff; A.ab0 = g.aff_b0; A.ad0 = g.aff_d0; A.ads = g.aff_ds;
+    A.out_aff = b.out_aff; A.og0 = g.out_g0; A.or0 = g.out_r0;
     A.tmpl = g.tmpl; A.nl = g.nl; A.ndof = g.ndof; A.fixed_base = g.fixed_base; A.chain = g.chain; A.nbl = g.nbody;
     A.link_f = s->d_link_f + (size_t)g.first_link * MG_LINK_F_N;
     A.link_i = s->d_link_i + (size_t)g.first_link * MG_LINK_I_N;
@@ -812,11 +818,11 @@ static MgArticArgs artic_args(mg_sim* s, const MgLaunch& l, const StepOut& O) {
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    A.dof_frc = l.feat & RT_FRC ? s->d_dof_frc : nullptr;
+    A.dof_frc = need & MG_NEED_DOF_FRC ? s->d_dof_frc : nullptr;
     A.out_rb = O.rb; A.out_root = O.root; A.out_dof = O.dof;   // chain groups only (s->layout.step_out_ok)
     A.out_body = O.out_body; A.out_root_row = O.out_root_row;
-    A.jfr = l.feat & RT_JFR ? 1 : 0;
-    if (l.feat & RT_ATTR) {
+    A.jfr = l.feat & RT_JFR ? 1 : 0;   // read by no kernel
+    if (need & MG_NEED_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
@@ -824,8 +830,9 @@ static MgArticArgs artic_args(mg_sim* s, const MgLaunch& l, const StepOut& O) {
 }
 
 // the coupled step of one env group (mg_env.hip)
-static MgEnvArgs env_args(mg_sim* s, const MgLaunch& l, const MgFusion::Step& fs) {
+static MgEnvArgs env_args(mg_sim* s, const MgLaunch& l, const MgBuild& b, const MgFusion::Step& fs) {
     const MgEnvGroup& g = s->layout.env_groups[l.group];
+    const unsigned need = mg_build_needs(b);
     MgEnvArgs A{};
     A.ne = g.count; A.nb = s->layout.nb; A.nd = s->layout.nd;
     A.env_i = s->d_env + (size_t)g.offset * MG_ENV_I_N;
@@ -851,24 +858,24 @@ static MgEnvArgs env_args(mg_sim* s, const MgLaunch& l, const MgFusion::Step& fs
     A.dof_props = s->d_dof_props;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    A.jfr = l.feat & RT_JFR ? 1 : 0;
-    if (l.feat & RT_ATTR) {
+    A.jfr = l.feat & RT_JFR ? 1 : 0;   // read by no kernel
+    if (need & MG_NEED_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
-    if (l.feat & RT_CREP) {   // the reporting builds
+    if (need & MG_NEED_CREP) {   // the reporting builds
         A.crep = s->d_crep_cenv + g.offset;
         A.crep_n = s->d_crep_cenv_n + g.offset;
         A.crep_body = s->d_slot_global;
         A.crep_stride = std::max(s->layout.n_coupled, 1);
     }
-    if (l.feat & RT_SENS) A.ctorque = s->d_ctorque;   // the contact-moment builds
-    A.dof_frc = l.feat & RT_FRC ? s->d_dof_frc : nullptr;
+    if (need & MG_NEED_CTORQUE) A.ctorque = s->d_ctorque;   // the contact-moment builds
+    A.dof_frc = need & MG_NEED_DOF_FRC ? s->d_dof_frc : nullptr;
     A.cap = {s->d_cap, s->d_cap_flags + cap_env0(s->layout) + g.offset};
     return A;
 }
 
-static MgPileArgs pile_args(const mg_sim* s, const MgLaunch& l) {
+static MgPileArgs pile_args(const mg_sim* s, const MgBuild& b) {
     MgPileArgs A{};
     A.ne = s->layout.n_pile; A.nb = s->layout.nb;
     A.pile_i = s->d_pile_i; A.pile_body = s->d_pile_body; A.pairs = s->d_pile_pairs; A.slots = s->d_pile_slots;
@@ -876,7 +883,7 @@ static MgPileArgs pile_args(const mg_sim* s, const MgLaunch& l) {
     A.shapes = s->d_shapes; A.hulls = s->d_hulls; A.shape_obb = s->d_shape_obb;
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    if (l.feat & RT_CREP) {   // the reporting build
+    if (mg_build_needs(b) & MG_NEED_CREP) {   // the reporting build
         A.crep = s->d_crep_pile;
         A.crep_n = s->d_crep_pile_n;
         A.crep_body = s->d_slot_global;
@@ -886,23 +893,24 @@ static MgPileArgs pile_args(const mg_sim* s, const MgLaunch& l) {
 }
 
 // the free-body step; a deferred root set (O.fs.root_src) is read by the kernel
-static MgRigidArgs rigid_args(const mg_sim* s, const MgLaunch& l, const StepOut& O) {
+static MgRigidArgs rigid_args(const mg_sim* s, const MgBuilds& b, const StepOut& O) {
+    const unsigned need = mg_build_needs(b.one) | mg_build_needs(b.multi);
     MgRigidArgs A{};
     A.nf = s->layout.nf_rigid; A.nf1 = s->layout.nf1; A.nb = s->layout.nb; A.free_ids = nullptr;   // internal slots 0..nf-1
     A.state = s->d_state; A.mass = s->d_mass; A.body_tmpl = s->d_body_tmpl;
     A.tbf = s->d_tbf; A.tbi = s->d_tbi; A.shapes = s->d_shapes; A.hulls = s->d_hulls;
     A.trec = s->d_trec; A.ntb = s->layout.ntb;
-    A.slot_rec = s->d_slot_rec;
+    A.slot_rec = need & MG_NEED_SLOT_REC ? (const MgSlotRec*)s->d_slot_rec : nullptr;
     A.box_only = s->layout.free_flags.empty() ? 0 : s->layout.free_flags[0];
     A.gpatch = s->d_gpatch;
     A.gstride = std::max(s->layout.nf1, 1);
     A.ext = s->ext_pending ? s->d_ext : nullptr;
     A.cforce = s->d_cforce;
-    if (l.feat & RT_ATTR) {
+    if (need & MG_NEED_ATTR) {
         A.attr_idx = s->d_attr_idx;
         A.attr = s->d_attr;
     }
-    if (l.feat & RT_CREP) {   // the reporting builds
+    if (need & MG_NEED_CREP) {   // the reporting builds
         A.crep = s->d_crep_free;
         A.crep_n = s->d_crep_free_n;
         A.crep_body = s->d_slot_global;
@@ -944,7 +952,7 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     const MgStep P = make_step(s->params);
-    s->rigid_form = -1;   // this simulate's, or none (mg_last_rigid_form)
+    s->builds.clear();   // this simulate's (mg_debug_step_builds, mg_last_rigid_form)
     // Under HIP stream capture (a hipGraph of the tensor-API step) the launches
     // are recorded as graph nodes; the timing events are left out (they would
     // become fixed nodes of the graph) and fetch_results does not block.
@@ -999,25 +1007,31 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     // (mg_fetch_host_state: the library's own buffer, so no caller-visible tensor changes)
     const MgFusion::Step fs = s->fuse.step(cid, R.step_writes_rows);
     const StepOut O = step_out(s, fs);
+    const MgRun run{mg_step_is_upz(P.n, P.t1, P.t2), s->ext_pending, O.rb || O.root, s->cus};
     for (const MgLaunch& l : R.launches) {
+        // which kernel at which form: the chooser's answer (mg_route.h), recorded as launched
+        const MgBuilds B = mg_route_builds(s->layout, l, run);
+        if (B.one.kernel) s->builds.push_back(B.one);
+        if (B.multi.kernel) s->builds.push_back(B.multi);
         hipError_t e = hipSuccess;
         switch (l.family) {
             case MG_FAM_ARTIC:
-                e = mg_launch_artic_step(P, artic_args(s, l, O), st);
+                e = B.one.kernel == MG_K_ARTIC_LANES ? mg_launch_artic_lanes(P, artic_args(s, l, B.one, O), B.one, st)
+                                                     : mg_launch_artic_chain(P, artic_args(s, l, B.one, O), B.one, st);
                 if (e != hipSuccess)
                     return fail(MG_ERR_DEVICE, "articulation step launch%s: %s",
                                 l.feat & RT_JFR ? " (joint friction)" : l.feat & RT_ATTR ? " (attractors)" : "", hipGetErrorString(e));
                 break;
             case MG_FAM_ENV:
-                e = mg_launch_env_step(P, env_args(s, l, fs), st);
+                e = mg_launch_env_step(P, env_args(s, l, B.one, fs), B.one, st);
                 if (e != hipSuccess) return fail(MG_ERR_DEVICE, "coupled env step launch: %s", hipGetErrorString(e));
                 break;
             case MG_FAM_PILE:
-                e = mg_launch_pile_step(P, pile_args(s, l), st);
+                e = mg_launch_pile_step(P, pile_args(s, B.one), B.one, st);
                 if (e != hipSuccess) return fail(MG_ERR_DEVICE, "pile step launch: %s", hipGetErrorString(e));
                 break;
             default:
-                HIP_TRY(mg_launch_rigid_step(P, rigid_args(s, l, O), st, &s->rigid_form));
+                HIP_TRY(mg_launch_rigid_step(P, rigid_args(s, B, O), B, st));
                 if (int rc_ = root_in_read(s, fs.root_src, st)) return rc_;
         }
     }
@@ -1455,7 +1469,22 @@ int32_t mg_debug_rcp_pairs(const float* d, float* out, int32_t n) {
     return MG_OK;
 }
 
-int32_t mg_last_rigid_form(mg_sim* s) { return s ? s->rigid_form : -1; }
+int32_t mg_last_rigid_form(mg_sim* s) {
+    if (s)
+        for (const MgBuild& b : s->builds)
+            if (b.kernel == MG_K_RIGID_STEP1) return mg_rigid_form_public(b.form);
+    return -1;
+}
+
+int32_t mg_debug_step_builds(mg_sim* s, int32_t* out, int32_t cap) {
+    if (!s || cap < 0 || (cap > 0 && !out)) return fail(MG_ERR_ARG, "mg_debug_step_builds: null sim or buffer");
+    for (size_t i = 0; i < s->builds.size() && (int32_t)i < cap; ++i) {
+        const MgBuild& b = s->builds[i];
+        const int32_t row[MG_STEP_BUILD_N] = {b.kernel, b.size, (int32_t)b.form};
+        std::memcpy(out + i * MG_STEP_BUILD_N, row, sizeof row);
+    }
+    return (int32_t)s->builds.size();
+}
 int32_t mg_num_free_bodies(mg_sim* s) { return s ? s->layout.nf : 0; }
 int32_t mg_num_articulations(mg_sim* s) { return s ? s->layout.nartic : 0; }
 int32_t mg_num_coupled_envs(mg_sim* s) { return s ? s->layout.n_coupled : 0; }

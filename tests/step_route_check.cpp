@@ -2,8 +2,9 @@
 // (test_isaacgym_amd/csrc/mg_route.h, included alone). One small layout built by
 // hand, every combination of the feature alphabet below, and for each the properties a route
 // must have: every stepped instance in exactly one launch, owners in their owner launch, the
-// split rows a stable permutation of the stepped rows, every launch's form (fed to mg_forms.h
-// the way the launchers do) built and carrying exactly the routed features or else a refusal,
+// split rows a stable permutation of the stepped rows, every launch's build (mg_route_builds: the
+// choosers of mg_forms.h, under every MgRun) built and carrying exactly the routed features or
+// else a refusal, the same across all MgRun, needing no buffer the plan's inputs do not allocate,
 // and the refusals' full texts and precedence as the engine has always reported them.
 // Prints "0 failures". The next feature adds one entry to the alphabet (main) and its expectation.
 #include "mg_route.h"
@@ -60,6 +61,7 @@ static MgLayout make_layout(bool step_out_ok) {
     for (int b : {(int)B_CA_FREE, (int)B_CB_FREE, (int)B_EF0, B_EF0 + 1}) L.body_class[b] = ATTR_ENV_FREE;
     for (int b = B_PILE0; b < B_STATIC; ++b) L.body_class[b] = ATTR_PILE;
     MgArticGroup g{};
+    g.fixed_base = 1;   // uncoupled articulations stand on a fixed base (a floating one steps in a coupled env)
     g.chain = 1; g.uni_mass = true; g.tmpl = 0; g.nl = 3; g.ndof = 2; g.aff = 1; g.step_offset = 0; g.step_count = 3;
     L.groups.push_back(g);
     g.chain = 0; g.uni_mass = false; g.tmpl = 1; g.aff = 0; g.step_offset = 3; g.step_count = 2;
@@ -87,57 +89,24 @@ static mg_attractor attractor(int body) {
     return a;
 }
 
-// the form a launcher chooses for these bits, as mg_env.hip / mg_chain.hip / mg_pile.hip / mg_rigid.hip call mg_forms.h
-static unsigned launcher_carries(const MgLayout& L, const MgLaunch& l, bool& built) {
-    const bool attr = l.feat & RT_ATTR, frc = l.feat & RT_FRC, sens = l.feat & RT_SENS, crep = l.feat & RT_CREP, jfr = l.feat & RT_JFR;
-    built = false;
-    switch (l.family) {
-        case MG_FAM_ARTIC: {
-            const MgArticGroup& g = L.groups[l.group];
-            if (jfr && (attr || !frc)) return 0;   // mg_launch_artic_lanes: hipErrorNotSupported
-            if (!jfr && !attr && g.chain && g.nl >= 2 && g.nl <= 4) {
-                const bool uni = g.uni_mass && !(l.feat & (RT_ATTR | RT_JFR));
-                bool ok = true;
-                unsigned f = 0;
-                for (int ext = 0; ext < 2; ++ext) {
-                    const MgChainForm c = mg_chain_form(l.count, ext, uni, !l.split && g.aff, frc);
-                    ok = ok && (c.quad ? k_artic_chain_q_built(g.nl, c.f) : k_artic_chain_built(g.nl, c.f));
-                    f = c.f;
-                }
-                built = ok;
-                return f & CF_FRC ? RT_FRC : 0;
-            }
-            const MgSizedForm k = k_artic_lanes_form(g.nl, g.ndof, attr, frc, jfr);
-            built = k_artic_lanes_built(k.maxl, mg_env_lanes(k.maxl), k.f);
-            return (k.f & LF_ATTR ? RT_ATTR : 0) | (k.f & LF_FRC ? RT_FRC : 0) | (k.f & LF_JFR ? RT_JFR : 0);
+// What a simulate can hand the choosers for launch `l`: every MgRun, with devices on both sides of
+// k_rigid_step1's wide threshold. Per launch the builds must not depend on it in what the route
+// relies on: built or not, and the routed features carried. Returns those two; `needs`: the
+// pointers any of the builds dereferences.
+static unsigned builds_of(const MgLayout& L, const MgLaunch& l, bool& built, unsigned& needs) {
+    const MgBuilds b0 = mg_route_builds(L, l, MgRun{false, false, false, 0});
+    built = b0.built();
+    needs = 0;
+    for (int m = 0; m < 8; ++m)
+        for (int cus : {0, 1, 256, 1 << 20}) {
+            const MgBuilds b = mg_route_builds(L, l, MgRun{(m & 1) != 0, (m & 2) != 0, (m & 4) != 0, cus});
+            CHECK(b.built() == built && mg_build_carried(b) == mg_build_carried(b0),
+                  "family %d group %d feat 0x%x: run %d, %d CUs changes built %d -> %d or carried 0x%x -> 0x%x", l.family, l.group,
+                  l.feat, m, cus, (int)built, (int)b.built(), mg_build_carried(b0), mg_build_carried(b));
+            CHECK((l.family == MG_FAM_FREE) == (b.multi.kernel != MG_K_NONE) && b.one.kernel != MG_K_NONE, "kernels of family %d", l.family);
+            needs |= mg_build_needs(b.one) | mg_build_needs(b.multi);
         }
-        case MG_FAM_ENV: {
-            const MgEnvGroup& g = L.env_groups[l.group];
-            const int nl = g.tmpl >= 0 ? g.nl : 0, ndof = g.tmpl >= 0 ? g.ndof : 0, fl = g.tmpl >= 0 ? g.floating : 0;
-            const int slots = ndof + (fl ? 6 : 0) + 6 * g.max_free;
-            const MgSizedForm k = k_env_step_form(nl, ndof, fl, slots, attr, frc, sens, crep, jfr);
-            built = k_env_step_built(k.maxl, mg_env_lanes(k.maxl), k.f);
-            return (k.f & EF_ATTR ? RT_ATTR : 0) | (k.f & EF_FRC ? RT_FRC : 0) | (k.f & EF_SENS ? RT_SENS : 0) |
-                   (k.f & EF_CREP ? RT_CREP : 0) | (k.f & EF_JFR ? RT_JFR : 0);
-        }
-        case MG_FAM_PILE: {
-            const unsigned f = k_pile_step_form(crep);
-            built = k_pile_step_built(f);
-            return f & PF_CREP ? RT_CREP : 0;
-        }
-        default: {
-            unsigned all = RT_ATTR | RT_CREP;
-            built = true;
-            for (int upz = 0; upz < 2; ++upz)
-                for (int blocks : {1, 100000}) {
-                    const unsigned f1 = k_rigid_step1_form(upz, blocks, 256, 1024, !crep, attr, crep, false, false);
-                    const unsigned f2 = k_rigid_step_form(upz, attr, crep);
-                    built = built && k_rigid_step1_built(f1) && k_rigid_step_built(f2, 8, true);
-                    all &= (f1 & f2 & RF_ATTR ? RT_ATTR : 0) | (f1 & f2 & RF_CREP ? RT_CREP : 0);
-                }
-            return all;
-        }
-    }
+    return mg_build_carried(b0);
 }
 
 static void run_case(const MgLayout& L, const std::vector<int>& attr_bodies, int sens_body, bool crep, int fric_dof, bool frc) {
@@ -238,11 +207,18 @@ static void run_case(const MgLayout& L, const std::vector<int>& attr_bodies, int
         last_family = l.family; last_group = l.group;
         CHECK(l.count > 0, "empty launch");
         bool built = false;
-        const unsigned carried = launcher_carries(L, l, built);
+        unsigned needs = 0;
+        const unsigned carried = builds_of(L, l, built, needs);
         const bool ok = built && carried == l.feat;
         dropped = dropped || !ok;
         CHECK(ok || !R.refusal_msg.empty(), "family %d group %d feat 0x%x: carried 0x%x built %d and no refusal", l.family,
               l.group, l.feat, carried, (int)built);
+        // an unrefused plan: every buffer a build dereferences exists under the plan's inputs
+        // (the sensor tables, the reporting records and the attractor table are allocated with their feature)
+        if (R.refusal_msg.empty())
+            CHECK((!(needs & MG_NEED_CTORQUE) || R.n_sens > 0) && (!(needs & MG_NEED_CREP) || crep) &&
+                      (!(needs & MG_NEED_ATTR) || !attrs.empty()),
+                  "family %d group %d feat 0x%x needs 0x%x: a buffer the plan's inputs do not allocate", l.family, l.group, l.feat, needs);
         CHECK(((l.feat & RT_FRC) != 0) == (frc || (l.feat & (RT_SENS | RT_CREP | RT_JFR))) || l.family >= MG_FAM_PILE, "FRC bit 0x%x", l.feat);
         if (l.family == MG_FAM_ARTIC) {
             const MgArticGroup& g = L.groups[l.group];

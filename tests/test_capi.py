@@ -25,7 +25,7 @@ def test_header_symbols_exported():
 
 def test_abi_version_and_errors():
     from test_isaacgym_amd import _native as N
-    assert N.lib.mg_abi_version() == 1
+    assert N.lib.mg_abi_version() == 2
     # null handles are rejected with a message, never dereferenced
     assert N.lib.mg_simulate(None, None) < 0
     assert "upload" in N.last_error() or "sim" in N.last_error()

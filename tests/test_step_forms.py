@@ -1,10 +1,12 @@
-"""Which build of a step kernel a launch gets (test_isaacgym_amd/csrc/mg_forms.h):
-tests/step_forms_check.cpp is built as a stand-alone host program that includes
-that header alone, and run. For each step kernel it runs the form function over
-every combination of its inputs, with block, CU and chain counts exactly at and
-one past each threshold, and checks that every chosen form is a built one, that
-every built form is chosen by some input (a dead build fails), and that the
-cases DESIGN.md names come out as documented. Its exit status is the verdict."""
+"""Which kernel, at which size and form, a step launch runs (the choosers of
+test_isaacgym_amd/csrc/mg_forms.h): tests/step_forms_check.cpp is built as a
+stand-alone host program that includes that header alone, and run. It runs every
+chooser over every combination of its inputs, every MgRun included, with block,
+CU and chain counts exactly at and one past each threshold and sizes at and past
+each limit, and checks that every chosen build is a built one, that every built
+form is chosen by some input (a dead build fails), that the pointers a build
+needs cover every bit of its own form word, and that the cases DESIGN.md names
+come out as documented. Its exit status is the verdict."""
 import os
 import subprocess
 

@@ -7,10 +7,12 @@ without an articulation, free bodies, a pile env, a static body) it plans every
 combination of attractors on none, one or two bodies of each class, a force sensor,
 contact reporting, joint friction and DOF forces, and checks that every stepped
 instance is in exactly one launch, that owners step in their owner launch, that the
-split rows are a stable permutation of the stepped rows, that every launch's form,
-chosen by mg_forms.h the way the launchers choose it, is built and carries exactly
-the routed features or else the route holds a refusal, and that the refusals keep
-their full texts and precedence. Its exit status is the verdict."""
+split rows are a stable permutation of the stepped rows, that every launch's build
+(mg_route_builds: the choosers of mg_forms.h, the call mg_simulate makes), under
+every MgRun, is built and carries exactly the routed features or else the route
+holds a refusal, that built and carried bits do not depend on the MgRun, that an
+unrefused launch's build needs no buffer the plan's inputs do not allocate, and that
+the refusals keep their full texts and precedence. Its exit status is the verdict."""
 import os
 import subprocess
 
