@@ -548,6 +548,41 @@ int32_t     mg_capacity_stats(mg_sim* sim, int64_t out[MG_CAP_N], int32_t reset,
 int32_t     mg_capacity_env_flags(mg_sim* sim, int32_t* dst_host, int32_t n_envs, void* stream);
 int32_t     mg_capacity_tracked(mg_sim* sim);
 
+/* ---- sleeping -----------------------------------------------
+ * PhysX sleeping by a displacement test over the wake window: an island (the
+ * moving bodies of one coupled or pile env; every other moving actor alone)
+ * none of whose bodies left its anchor pose by more than
+ * tol = window * sqrt(2 * threshold) for W = max(1, lround(window / dt)) frames
+ * falls asleep: from then on its rigid-body rows and DOF rows are constant bit
+ * for bit, its velocities exactly 0, until it is woken. A sleeping island is
+ * still stepped and the result thrown away by k_sleep_pass (one launch per
+ * island size class after the frame's step launches, captured into graphs with
+ * them); its net contact force, DOF force, force sensor and contact list rows
+ * are those of the discarded step (the resting forces). OFF by default.
+ *
+ * mg_set_sleeping: threshold (m^2/s^2, PhysX's sleepThreshold) and window (s,
+ * PhysX's wake counter reset) both > 0 turn sleeping on; a non-positive or
+ * non-finite value turns it off. Before or after the upload; timers start at 0
+ * and the anchors are taken at the next pass. It adds launches to a simulate, so
+ * it is refused (MG_ERR_STATE) when the last mg_simulate was captured into a
+ * graph. While sleeping is on mg_step_out_supported is 0.
+ * Wakes (asleep := 0, timer := 0), in stream order before the data they come
+ * with: mg_set_actor_root_state, mg_set_dof_state and the DOF target / force sets
+ * wake the islands of the indexed actors (all islands when not indexed);
+ * mg_set_rigid_body_state, mg_set_dof_props and mg_set_sim_params wake all;
+ * mg_apply_rigid_body_force wakes the islands of the bodies with a non-zero
+ * row; an attractor table or target set wakes the islands of those attractors'
+ * bodies. mg_wake: the islands of the n actors of actor_idx (host memory when
+ * idx_host, else device), all islands when actor_idx is NULL.
+ * mg_sleep_state: dst[a] = 1 when actor a's island is asleep, else 0, for the
+ * model's actors (device memory, or host when dst_host, then it waits).
+ * mg_sleep_stats: out[0] islands, out[1] islands asleep at the last pass (waits
+ * for the device), out[2] pass launches per simulate (0: sleeping is off). */
+int32_t     mg_set_sleeping(mg_sim* sim, float threshold, float window);
+int32_t     mg_wake(mg_sim* sim, const int32_t* actor_idx, int32_t n, int32_t idx_host, void* stream);
+int32_t     mg_sleep_state(mg_sim* sim, int32_t* dst, int32_t dst_host, void* stream);
+int32_t     mg_sleep_stats(mg_sim* sim, int32_t out[3]);
+
 /* ---- step fusion ------------------------------------------------------------
  * MG_FUSE_ROOT_SET: the deferred root-state set described above.
  * MG_FUSE_DOF_TARGETS: a device-resident, non-indexed mg_set_dof_position_target /
@@ -653,8 +688,8 @@ int32_t     mg_debug_artic_groups(mg_sim* sim, int32_t* out, int32_t cap);
  * no sim and no device: the call touches no GPU. NULL + mg_last_error() when
  * the model is refused, with mg_upload_model's message. mg_debug_layout_table
  * points *data at table `which` (owned by the plan, valid until it is freed)
- * and sets *count to its elements: int32, except PILE_PAIRS (uint32) and
- * CENV_CTAB_OFF (int64). SCALARS: MG_LAYOUT_HEAD_N ints — bodies, actors,
+ * and sets *count to its elements: int32, except PILE_PAIRS (uint32),
+ * CENV_CTAB_OFF (int64) and BODY_K (float32). SCALARS: MG_LAYOUT_HEAD_N ints — bodies, actors,
  * DOFs, nf, nf1, nf_rigid, coupled envs, pile envs, max_actor_dofs, roots_free,
  * step_out_ok, articulation groups, env groups — then MG_LAYOUT_GROUP_N per
  * articulation group (chain, aff, aff_b0, aff_d0, aff_ds, out_aff, out_g0,
@@ -677,6 +712,18 @@ typedef struct mg_layout mg_layout;
  * build; [0]: each one's shape is a box at the body origin with the body's
  * orientation, or absent (the box-only build, mg_last_rigid_form) */
 #define MG_LAYOUT_FREE_FLAGS    12
+/* sleeping islands: storage slot -> island (-1: static), actor
+ * -> island, the CSR island -> storage slots and island -> DOFs, {islands, first
+ * island of the 2..16-body class, of the larger class}, and per storage slot
+ * k_b = 4 r_b^2 (float32) */
+#define MG_LAYOUT_BODY_ISLAND   13
+#define MG_LAYOUT_ACTOR_ISLAND  14
+#define MG_LAYOUT_ISLAND_BODY0  15
+#define MG_LAYOUT_ISLAND_BODY   16
+#define MG_LAYOUT_ISLAND_DOF0   17
+#define MG_LAYOUT_ISLAND_DOF    18
+#define MG_LAYOUT_ISLAND_CLASS  19
+#define MG_LAYOUT_BODY_K        20
 #define MG_LAYOUT_HEAD_N        13
 #define MG_LAYOUT_GROUP_N       14
 #define MG_LAYOUT_ENVGROUP_N    5

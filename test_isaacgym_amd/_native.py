@@ -33,6 +33,9 @@ MG_DEBUG_GROUP_N = 8       # include/migym.h mg_debug_artic_groups
  MG_LAYOUT_PAIRS, MG_LAYOUT_PILE_ROWS, MG_LAYOUT_PILE_BODY, MG_LAYOUT_PILE_SLOTS, MG_LAYOUT_PILE_PAIRS,
  MG_LAYOUT_CENV_ROW, MG_LAYOUT_CENV_CTAB_OFF, MG_LAYOUT_FREE_FLAGS) = range(13)
 MG_LAYOUT_HEAD_N, MG_LAYOUT_GROUP_N, MG_LAYOUT_ENVGROUP_N = 13, 14, 5
+# the sleeping islands' tables; BODY_K is float32
+(MG_LAYOUT_BODY_ISLAND, MG_LAYOUT_ACTOR_ISLAND, MG_LAYOUT_ISLAND_BODY0, MG_LAYOUT_ISLAND_BODY, MG_LAYOUT_ISLAND_DOF0,
+ MG_LAYOUT_ISLAND_DOF, MG_LAYOUT_ISLAND_CLASS, MG_LAYOUT_BODY_K) = range(13, 21)
 # mg_last_rigid_form (include/migym.h): bits of the last single-shape free-body launch
 MG_RIGID_FORM_WIDE, MG_RIGID_FORM_REC, MG_RIGID_FORM_BOX = 1, 2, 4
 # mg_debug_step_builds (include/migym.h): MG_KERNEL_* by value, ints per row
@@ -243,6 +246,10 @@ def _load():
         "mg_capacity_stats": (i32, [vp, vp, i32, vp]),
         "mg_capacity_env_flags": (i32, [vp, vp, i32, vp]),
         "mg_capacity_tracked": (i32, [vp]),
+        "mg_set_sleeping": (i32, [vp, ctypes.c_float, ctypes.c_float]),
+        "mg_wake": (i32, [vp, vp, i32, i32, vp]),
+        "mg_sleep_state": (i32, [vp, vp, i32, vp]),
+        "mg_sleep_stats": (i32, [vp, vp]),
         "mg_debug_plan_layout": (vp, [ctypes.POINTER(MgSimParams), ctypes.POINTER(MgModel)]),
         "mg_debug_layout_table": (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]),
         "mg_debug_free_layout": (None, [vp]),
@@ -277,6 +284,7 @@ EXPORTED_SYMBOLS = (
     "mg_set_contact_reporting", "mg_contact_reporting", "mg_refresh_rigid_contacts",
     "mg_joint_friction_stats",
     "mg_capacity_stats", "mg_capacity_env_flags", "mg_capacity_tracked",
+    "mg_set_sleeping", "mg_wake", "mg_sleep_state", "mg_sleep_stats",
     "mg_debug_plan_layout", "mg_debug_layout_table", "mg_debug_free_layout", "mg_last_error_code",
     "mg_last_rigid_form", "mg_debug_step_builds", "mg_debug_rcp_pairs",
 )
@@ -299,7 +307,7 @@ def check(rc, what):
 def plan_layout(params, model, tables=range(12)):
     """The layout plan of a model (mg_debug_plan_layout; no GPU): {table id: numpy array}, or
     MigymError with the library's refusal. `tables`: the ids to return (the first twelve by
-    default; MG_LAYOUT_FREE_FLAGS on request)."""
+    default; MG_LAYOUT_FREE_FLAGS and the island tables on request)."""
     h = lib.mg_debug_plan_layout(ctypes.byref(params), ctypes.byref(model))
     if not h:
         raise MigymError(last_error())
@@ -308,7 +316,8 @@ def plan_layout(params, model, tables=range(12)):
         for which in tables:
             data, n = ctypes.c_void_p(), ctypes.c_int64()
             check(lib.mg_debug_layout_table(h, which, ctypes.byref(data), ctypes.byref(n)), "mg_debug_layout_table")
-            dt = {MG_LAYOUT_PILE_PAIRS: np.uint32, MG_LAYOUT_CENV_CTAB_OFF: np.int64}.get(which, np.int32)
+            dt = {MG_LAYOUT_PILE_PAIRS: np.uint32, MG_LAYOUT_CENV_CTAB_OFF: np.int64,
+                  MG_LAYOUT_BODY_K: np.float32}.get(which, np.int32)
             buf = ctypes.string_at(data.value, n.value * np.dtype(dt).itemsize) if n.value else b""
             out[which] = np.frombuffer(buf, dt).copy()
         return out

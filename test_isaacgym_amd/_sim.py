@@ -31,6 +31,44 @@ if hasattr(torch._C, "_cuda_getCurrentRawStream"):
 
 
 
+# sleeping: PhysX's sleep threshold (m^2/s^2) and wake window (s), DESIGN.md §4
+SLEEP_DEFAULTS = (5e-5, 0.4)
+
+
+def check_sleep_values(threshold, window):
+    """(threshold, window) as floats, or ValueError: both must be finite and
+    positive, also once rounded to the float32 the library takes."""
+    try:
+        thr, win = float(threshold), float(window)
+    except (TypeError, ValueError):
+        raise ValueError("sleeping: threshold and window must be numbers, got %r, %r" % (threshold, window))
+    with np.errstate(over="ignore"):
+        ok = all(np.isfinite(np.float32(v)) and np.float32(v) > 0 for v in (thr, win))
+    if not ok:
+        raise ValueError("sleeping: threshold (m^2/s^2) and window (s) must be finite and positive, got %r, %r"
+                         % (threshold, window))
+    return thr, win
+
+
+def parse_sleep_env(text):
+    """MIGYM_SLEEP at create_sim: unset, empty or "0": off (None); "1": on with
+    SLEEP_DEFAULTS; "threshold,window": on with those values. Anything else is a
+    ValueError."""
+    t = (text or "").strip()
+    if t in ("", "0"):
+        return None
+    if t == "1":
+        return SLEEP_DEFAULTS
+    parts = t.split(",")
+    if len(parts) != 2:
+        raise ValueError("MIGYM_SLEEP=%r: expected 0, 1 or threshold,window" % text)
+    try:
+        thr, win = float(parts[0]), float(parts[1])
+    except ValueError:
+        raise ValueError("MIGYM_SLEEP=%r: expected 0, 1 or threshold,window" % text)
+    return check_sleep_values(thr, win)
+
+
 _warned_multishape = [False]
 
 
@@ -280,6 +318,9 @@ class Sim:
         self.capacity_check = os.environ.get("MIGYM_CAPACITY_CHECK", "1") != "0"
         self.capacity_warned = set()
         self.capacity_tracked = None
+        # sleeping (gym.set_sleeping): None (off, the default) or
+        # (threshold, window); MIGYM_SLEEP sets the default for new sims
+        self.sleeping = parse_sleep_env(os.environ.get("MIGYM_SLEEP"))
 
     @property
     def renderer(self):
@@ -626,6 +667,8 @@ class Sim:
             if not handle:
                 raise N.MigymError("mg_create_sim: " + N.last_error())
             self.native = handle
+            if self.sleeping is not None:
+                N.check(N.lib.mg_set_sleeping(handle, *self.sleeping), "mg_set_sleeping")
             N.check(N.lib.mg_upload_model(handle, ctypes.byref(self.mg_model())), "mg_upload_model")
             if self.host_stage is not None and os.environ.get("MIGYM_HOST_STAGE", "mapped") != "copy":
                 # the sim's own device-mapped host stage (mg_host_stage): the
@@ -850,6 +893,52 @@ class Sim:
         out = (ctypes.c_int32 * 3)()
         N.check(N.lib.mg_joint_friction_stats(self.require_native("joint_friction_stats"), out),
                 "mg_joint_friction_stats")
+        return tuple(int(v) for v in out)
+
+    def set_sleeping(self, enabled, threshold, window):
+        """gym.set_sleeping: checked here, kept for the upload, sent at once to
+        an uploaded model (mg_set_sleeping)."""
+        want = check_sleep_values(threshold, window) if enabled else None
+        if self.native is not None:
+            N.check(N.lib.mg_set_sleeping(self.native, *(want or (0.0, 0.0))), "mg_set_sleeping")
+        self.sleeping = want
+
+    def _actor_indices(self, indices, what):
+        """`indices` (a sequence, numpy array or torch tensor of actor indices) as a
+        host int32 array, or ValueError."""
+        if isinstance(indices, torch.Tensor):
+            indices = indices.detach().cpu().numpy()
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1))
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("%s: actor indices must be integers" % what)
+        idx = idx.astype(np.int32)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.num_actors):
+            raise ValueError("%s: actor index out of range (the sim has %d actors)" % (what, self.num_actors))
+        return idx
+
+    def sleeping_actors(self):
+        """gym.get_sleeping_actors: per actor, is its island asleep (mg_sleep_state)?"""
+        self.finalize()
+        out = np.zeros(max(self.num_actors, 1), dtype=np.int32)
+        if self.sleeping is not None:
+            N.check(N.lib.mg_sleep_state(self.require_native("get_sleeping_actors"), out.ctypes.data, 1, self.stream()),
+                    "mg_sleep_state")
+        return out[:self.num_actors].astype(bool)
+
+    def wake_actors(self, indices=None):
+        """gym.wake_actors: the islands of `indices`, or every island (mg_wake)."""
+        self.finalize()
+        idx = None if indices is None else self._actor_indices(indices, "wake_actors")
+        if self.sleeping is None or self.native is None:
+            return
+        N.check(N.lib.mg_wake(self.native, None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx), 1,
+                              self.stream()), "mg_wake")
+
+    def sleep_stats(self):
+        """(islands, islands asleep at the last pass, pass launches per simulate);
+        all 0 while sleeping is off (mg_sleep_stats)."""
+        out = (ctypes.c_int32 * 3)()
+        N.check(N.lib.mg_sleep_stats(self.require_native("sleep_stats"), out), "mg_sleep_stats")
         return tuple(int(v) for v in out)
 
     def capacity_report(self, reset=False):

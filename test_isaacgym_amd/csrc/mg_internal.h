@@ -518,6 +518,31 @@ hipError_t mg_launch_env_step_sens(const MgBuild& b, hipStream_t s, const MgStep
 hipError_t mg_launch_env_step_crep(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
 hipError_t mg_launch_env_step_jfr(const MgBuild& b, hipStream_t s, const MgStep& P, const MgEnvArgs& A);
 hipError_t mg_launch_artic_lanes_jfr(const MgBuild& b, hipStream_t s, const MgStep& P, const MgArticArgs& A);
+// Sleeping (mg_sleep.hip): the pass after a frame's step launches, and the wakes.
+struct MgSleepArgs {
+    int nb, nd;
+    int i0, n;                 // the launch's islands: i0 .. i0 + n - 1 (one size class)
+    int window;                // W: frames at rest before an island falls asleep
+    float tol2;                // squared displacement over the window that counts as movement
+    const int *body0, *body;   // CSR island -> storage slots
+    const int *dof0, *dof;     // CSR island -> DOFs
+    const float* body_k;       // [nb] 4 r_b^2
+    float* state;              // [13][nb]
+    float* dofs;               // [2][nd]
+    int *timer, *asleep;       // [islands]; timer < 0: no anchor taken yet
+    float* anchor;             // [7][nb] anchor poses (the frozen poses of sleeping islands)
+    float* dof_q;              // [nd] the DOF positions of sleeping islands
+};
+// one launch per size class present: lanes = 1, 16 or 64 per island
+hipError_t mg_launch_sleep_pass(const MgSleepArgs& A, int lanes, hipStream_t s);
+// wakes island table[idx[t]] (table NULL: idx[t] itself; idx NULL: t itself), t < n; entries out
+// of [0, n_table) / islands out of [0, n_island) are skipped
+hipError_t mg_launch_wake(const int* idx, int n, const int* table, int n_table, int n_island, int* timer, int* asleep,
+                          hipStream_t s);
+// wakes the islands of the slots whose applied wrench row (ext [6][nb]) is not zero
+hipError_t mg_launch_wake_ext(const float* ext, int nb, const int* body_island, int* timer, int* asleep, hipStream_t s);
+// dst[a] = actor a's island is asleep (0 / 1; no island: 0)
+hipError_t mg_launch_sleep_actors(const int* actor_island, int na, const int* asleep, int* dst, hipStream_t s);
 hipError_t mg_launch_sensor_mark(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_force_sensor(const MgSensorArgs& A, hipStream_t s);
 hipError_t mg_launch_pile_step(const MgStep& P, const MgPileArgs& A, const MgBuild& b, hipStream_t s);

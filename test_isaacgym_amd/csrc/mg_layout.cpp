@@ -788,6 +788,100 @@ void plan_free_flags(const MgLayoutSizes& z, MgLayout& L) {
     L.free_flags.assign(1, box_only ? 1 : 0);
 }
 
+// ---- step 6: sleeping islands
+
+// a shape's reach about its body's origin, |p_s| + extent_s (the extents of plan_trec)
+double shape_reach(const float* sr) {
+    double ext = 0.0;
+    switch ((int)sr[0]) {
+        case MG_SHAPE_SPHERE: ext = sr[1]; break;
+        case MG_SHAPE_BOX: ext = std::sqrt((double)sr[1] * sr[1] + (double)sr[2] * sr[2] + (double)sr[3] * sr[3]); break;
+        case MG_SHAPE_CAPSULE: ext = (double)sr[1] + sr[2]; break;
+        case MG_SHAPE_CONVEX: ext = sr[1]; break;
+        default: break;
+    }
+    return std::sqrt((double)sr[4] * sr[4] + (double)sr[5] * sr[5] + (double)sr[6] * sr[6]) + ext;
+}
+
+void plan_islands(const mg_model* m, MgLayout& L, const Work& w) {
+    const int nb = L.nb, na = L.na;
+    // the bodies of each actor (global ids first .. first + count - 1)
+    std::vector<int> first(na), count(na, 1);
+    for (int a = 0; a < na; ++a) {
+        first[a] = m->actor_root_body[a];
+        const int k = L.body_artic[first[a]];
+        if (k >= 0) {
+            first[a] = L.artic_info[k].g0;
+            count[a] = L.groups[L.artic_info[k].tmpl].nbody;
+        }
+    }
+    // bounding radii
+    std::vector<double> reach(nb, -1.0);
+    for (int b = 0; b < nb; ++b) {
+        int s0, ns;
+        shape_range(m, b, &s0, &ns);
+        for (int s = s0; s < s0 + ns; ++s)
+            reach[b] = std::max(reach[b], shape_reach(m->shapes + (size_t)s * MG_SHAPE_STRIDE));
+    }
+    L.body_k.assign(nb, 0.0f);
+    for (int a = 0; a < na; ++a) {
+        double most = 0.0;
+        for (int b = first[a]; b < first[a] + count[a]; ++b) most = std::max(most, reach[b]);
+        for (int b = first[a]; b < first[a] + count[a]; ++b) {
+            const double r = reach[b] >= 0.0 ? reach[b] : most;
+            L.body_k[L.perm[b]] = std::isfinite(r) ? (float)(4.0 * r * r) : 0.0f;
+        }
+    }
+    // the islands as their actors, in actor order: one per coupled or pile env, one per other moving actor
+    std::vector<std::vector<int>> members;
+    std::map<int, int> of_env;
+    for (int a = 0; a < na; ++a) {
+        const int r0 = m->actor_root_body[a];
+        if (m->body_kind[r0] == MG_BODY_STATIC) continue;
+        if (w.coupled_body[r0]) {
+            const int e = m->actor_coll[(size_t)a * MG_ACOLL_N + 0];
+            auto it = of_env.find(e);
+            if (it == of_env.end()) {
+                it = of_env.emplace(e, (int)members.size()).first;
+                members.emplace_back();
+            }
+            members[it->second].push_back(a);
+        } else {
+            members.push_back({a});
+        }
+    }
+    struct Isl { int cls, slot0; std::vector<int> slots, dofs; const std::vector<int>* actors; };
+    std::vector<Isl> isl(members.size());
+    for (size_t i = 0; i < members.size(); ++i) {
+        Isl& I = isl[i];
+        I.actors = &members[i];
+        for (int a : members[i]) {
+            for (int b = first[a]; b < first[a] + count[a]; ++b) I.slots.push_back(L.perm[b]);
+            for (int d = m->actor_dof[a]; d < m->actor_dof[a + 1]; ++d) I.dofs.push_back(d);
+        }
+        std::sort(I.slots.begin(), I.slots.end());
+        I.slot0 = I.slots[0];
+        I.cls = I.slots.size() == 1 ? 0 : I.slots.size() <= 16 ? 1 : 2;
+    }
+    std::sort(isl.begin(), isl.end(), [](const Isl& x, const Isl& y) { return x.cls != y.cls ? x.cls < y.cls : x.slot0 < y.slot0; });
+    L.n_island = (int)isl.size();
+    L.body_island.assign(nb, -1);
+    L.actor_island.assign(na, -1);
+    L.island_body0.assign(1, 0);
+    L.island_dof0.assign(1, 0);
+    for (int c = 0; c < 4; ++c) L.island_class0[c] = L.n_island;
+    for (int i = 0; i < L.n_island; ++i) {
+        const Isl& I = isl[i];
+        for (int c = 0; c <= I.cls; ++c) L.island_class0[c] = std::min(L.island_class0[c], i);
+        for (int s : I.slots) L.body_island[s] = i;
+        for (int a : *I.actors) L.actor_island[a] = i;
+        L.island_body.insert(L.island_body.end(), I.slots.begin(), I.slots.end());
+        L.island_dof.insert(L.island_dof.end(), I.dofs.begin(), I.dofs.end());
+        L.island_body0.push_back((int)L.island_body.size());
+        L.island_dof0.push_back((int)L.island_dof.size());
+    }
+}
+
 }  // namespace
 
 int mg_plan_layout(const mg_sim_params& p, const mg_model& model, const MgLayoutSizes& z, MgLayout& L, std::string& err) {
@@ -804,5 +898,6 @@ int mg_plan_layout(const mg_sim_params& p, const mg_model& model, const MgLayout
     plan_trec(m, z, L);
     plan_slot_tables(m, L);
     plan_free_flags(z, L);
+    plan_islands(m, L, w);
     return MG_OK;
 }

@@ -101,6 +101,22 @@ struct MgLayout {
     std::vector<int> cenv_ctab_n;
     // host copies of the model's tables
     std::vector<int> link_i, atmpl, body_tmpl, tbi, actor_dof;
+
+    // Sleeping islands: the bodies that rest and wake as one. The moving actors
+    // of a coupled or pile env form one island (every link of its articulation, every free body);
+    // every other moving actor is an island of its own; static bodies have none (-1). Islands are
+    // sorted by size class (1 body, 2..16, more: the lanes k_sleep_pass gives each) and within a
+    // class by first storage slot, so the islands of the free-body kernel's bodies are 0..nf_rigid-1
+    // in slot order and island i's body is slot i.
+    int n_island = 0;
+    int island_class0[4] = {0, 0, 0, 0};        // first island of each size class, and n_island
+    std::vector<int> body_island;               // [nb] storage slot -> island, -1: static
+    std::vector<int> actor_island;              // [na] actor -> island of its root, -1: static
+    std::vector<int> island_body0, island_body; // CSR: island -> its storage slots (ascending)
+    std::vector<int> island_dof0, island_dof;   // CSR: island -> its DOFs (ascending)
+    // [nb] by storage slot: k_b = 4 r_b^2, r_b the body's bounding radius about its origin (the
+    // largest |p_s| + extent_s over its shapes; a body without shapes takes its actor's largest)
+    std::vector<float> body_k;
 };
 
 // Plans the layout of `m` under `p`. Returns MG_OK, or the error code with its

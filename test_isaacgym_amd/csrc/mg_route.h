@@ -59,6 +59,7 @@ struct MgRouteIn {
     bool crep = false;
     const float* dof_props = nullptr;   // [nd][MG_DOFPROP_N] global DOF order; null: no DOF has friction
     int dof_frc_n = 0;
+    bool sleep = false;                 // sleeping is on (mg_set_sleeping): k_sleep_pass rewrites rows after the step
 };
 
 struct MgRoute {
@@ -77,7 +78,8 @@ struct MgRoute {
     int n_attr = 0, dof_frc_n = 0;
     bool crep = false;
     // the step may write its rows itself (the fused refresh, the host stage): every kernel that
-    // steps a body writes its rows, none is an attractor, reporting or joint-friction build
+    // steps a body writes its rows, none is an attractor, reporting or joint-friction build, and
+    // no sleep pass follows the step (it restores the rows of sleeping islands)
     bool step_writes_rows = false;
     // mg_joint_friction_stats: friction DOFs, instances in the lanes friction launches, envs of coupled friction groups
     int jfr_ndof = 0, jfr_lanes = 0, jfr_envs = 0;
@@ -361,6 +363,6 @@ inline int mg_plan_route(const MgLayout& L, const MgRouteIn& in, MgRoute& R, std
     }
     R.refusal_msg = !attr_refusal.empty() ? attr_refusal : !R.sens_refusal.empty() ? R.sens_refusal : launch_refusal;
     R.refusal = R.refusal_msg.empty() ? MG_OK : MG_ERR_UNSUPPORTED;
-    R.step_writes_rows = L.step_out_ok && in.n_attr == 0 && !in.crep && R.jfr_ndof == 0;
+    R.step_writes_rows = L.step_out_ok && in.n_attr == 0 && !in.crep && R.jfr_ndof == 0 && !in.sleep;
     return MG_OK;
 }

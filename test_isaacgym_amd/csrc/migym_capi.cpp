@@ -226,6 +226,18 @@ struct CrepBufs {
     DevBuf<mg_rigid_contact> d_crep_out;
     DevBuf<int> d_crep_hdr;            // [2]
 };
+// sleeping (mg_set_sleeping, mg_sleep.hip): the island tables of the layout plan
+// and the pass's state, allocated while sleeping is on
+struct SleepBufs {
+    DevBuf<int> d_body0, d_body, d_dof0, d_dof;   // CSR island -> storage slots / DOFs
+    DevBuf<int> d_body_island, d_actor_island;    // [nb] slot -> island, [na] actor -> island (-1: none)
+    DevBuf<float> d_body_k;                       // [nb] 4 r_b^2
+    DevBuf<int> d_timer, d_asleep;                // [islands]; timer -1: no anchor taken yet
+    DevBuf<float> d_anchor;                       // [7][nb]
+    DevBuf<float> d_dof_q;                        // [nd]
+    DevBuf<int> d_idx;                            // mg_sleep_state's [na] device copy, the host wakes' island lists
+    size_t idx_n = 0;
+};
 
 }  // namespace
 
@@ -321,6 +333,12 @@ struct mg_sim : Model, SensBufs, CrepBufs {
     int crep_capacity = 0;
     HostBuf<int> h_crep_hdr;            // [2] mapped, page-locked
     int* d_crep_hdr_alias = nullptr;      // its device address
+
+    // sleeping (mg_set_sleeping): off unless both figures are positive; the
+    // buffers exist while it is on and a model is uploaded
+    bool sleep_on = false;
+    float sleep_threshold = 0.0f, sleep_window = 0.0f;
+    SleepBufs sleep;
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false;          // mg_set_kernel_timing: events around eager launches
@@ -503,6 +521,54 @@ int apply_tgt(mg_sim* s, int k, const MgFusion::Apply& a, hipStream_t st) {
     return MG_OK;
 }
 
+// ---- sleeping ----
+// the island tables and a fresh pass state (no island asleep, no anchor taken) for layout L
+int sleep_alloc(const MgLayout& L, SleepBufs& B) {
+    HIP_TRY(B.d_body0.upload(L.island_body0));
+    HIP_TRY(B.d_body.upload(L.island_body));
+    HIP_TRY(B.d_dof0.upload(L.island_dof0));
+    HIP_TRY(B.d_dof.upload(L.island_dof));
+    HIP_TRY(B.d_body_island.upload(L.body_island));
+    HIP_TRY(B.d_actor_island.upload(L.actor_island));
+    HIP_TRY(B.d_body_k.upload(L.body_k));
+    HIP_TRY(B.d_timer.upload(std::vector<int>((size_t)L.n_island, -1)));
+    HIP_TRY(B.d_asleep.zero((size_t)L.n_island));
+    HIP_TRY(B.d_anchor.zero((size_t)7 * L.nb));
+    HIP_TRY(B.d_dof_q.zero((size_t)L.nd));
+    HIP_TRY(B.d_idx.alloc((size_t)std::max(L.na, 1)));
+    B.idx_n = (size_t)std::max(L.na, 1);
+    return MG_OK;
+}
+bool sleeping(const mg_sim* s) { return s->sleep_on && s->uploaded; }
+// wake the islands of the actors didx[0..n) (device memory; null: every island), in stream order
+int sleep_wake(mg_sim* s, const int* didx, int n, hipStream_t st) {
+    if (!sleeping(s)) return MG_OK;
+    const MgLayout& L = s->layout;
+    if (!didx) HIP_TRY(mg_launch_wake(nullptr, L.n_island, nullptr, 0, L.n_island, s->sleep.d_timer, s->sleep.d_asleep, st));
+    else HIP_TRY(mg_launch_wake(didx, n, s->sleep.d_actor_island, L.na, L.n_island, s->sleep.d_timer, s->sleep.d_asleep, st));
+    return MG_OK;
+}
+// the wake of a call that has no stream (mg_set_dof_props, mg_set_sim_params, the attractor sets):
+// islands `isl` (null: all), after the device's pending work and done when it returns
+int sleep_wake_sync(mg_sim* s, const std::vector<int>* isl) {
+    if (!sleeping(s) || (isl && isl->empty())) return MG_OK;
+    const MgLayout& L = s->layout;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (isl) {
+        if (isl->size() > s->sleep.idx_n) {
+            s->sleep.idx_n = 0;
+            HIP_TRY(s->sleep.d_idx.alloc(isl->size()));
+            s->sleep.idx_n = isl->size();
+        }
+        HIP_TRY(hipMemcpy(s->sleep.d_idx, isl->data(), isl->size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(mg_launch_wake(isl ? (const int*)s->sleep.d_idx : nullptr, isl ? (int)isl->size() : L.n_island, nullptr, 0, L.n_island,
+                           s->sleep.d_timer, s->sleep.d_asleep, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return MG_OK;
+}
+
 int set_dof_columns(mg_sim* s, const float* src, int src_host, int ncol, float* dst0, float* dst1,
                     const int* idx, int n_idx, hipStream_t st) {
     if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
@@ -514,6 +580,7 @@ int set_dof_columns(mg_sim* s, const float* src, int src_host, int ncol, float* 
     const int* didx;
     int rc = stage_src(s, src, src_host, (size_t)s->layout.nd * ncol, idx, n_idx, st, &dsrc, &didx);
     if (rc) return rc;
+    if ((rc = sleep_wake(s, idx ? didx : nullptr, n_idx, st))) return rc;   // autowake: the set actors' islands
     float* dst[2] = {dst0, dst1};
     if (idx)
         HIP_TRY(mg_launch_scatter_dofs(dsrc, ncol, s->d_actor_dof, didx, n_idx, s->layout.na, s->layout.max_actor_dofs, dst, st));
@@ -584,7 +651,7 @@ void mg_destroy_sim(mg_sim* s) {
 int32_t mg_set_sim_params(mg_sim* s, const mg_sim_params* p) {
     if (!s || !p) return fail(MG_ERR_ARG, "null argument");
     s->params = *p;
-    return MG_OK;
+    return sleep_wake_sync(s, nullptr);
 }
 
 // k_artic_chain's shared constants (mg_chainlink.h). Link mass constants and
@@ -635,6 +702,7 @@ static MgRouteIn route_in(const mg_sim* s) {
     in.crep = s->route.crep;
     in.dof_props = s->dof_props.empty() ? nullptr : s->dof_props.data();
     in.dof_frc_n = s->route.dof_frc_n;
+    in.sleep = s->sleep_on;
     return in;
 }
 static int plan_route(const MgLayout& L, const MgRouteIn& in, MgRoute& R) {
@@ -674,6 +742,7 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     M.dof_props.assign(m->dof_props, m->dof_props + (size_t)nd * MG_DOFPROP_N);
     MgRouteIn rin;
     rin.dof_props = nd > 0 ? M.dof_props.data() : nullptr;
+    rin.sleep = s->sleep_on;
     if (int rc_ = plan_route(L, rin, M.route)) return rc_;
 
     // bodies, templates, shapes
@@ -729,11 +798,15 @@ int32_t mg_upload_model(mg_sim* s, const mg_model* m) {
     }
     HIP_TRY(M.d_cap.zero(MG_CAP_N));
     HIP_TRY(M.d_cap_flags.zero((size_t)cap_units(L)));
+    SleepBufs SB;   // sleeping was turned on before the upload
+    if (s->sleep_on)
+        if (int rc_ = sleep_alloc(L, SB)) return rc_;
     HIP_TRY(hipDeviceSynchronize());
     // ---- commit (nothing below fails); the initial state went to the device
     std::vector<float>().swap(L.state0);
     std::vector<float>().swap(L.mass0);
     static_cast<Model&>(*s) = std::move(M);
+    s->sleep = std::move(SB);
     s->uploaded = true;
     return MG_OK;
 }
@@ -1037,6 +1110,25 @@ int32_t mg_simulate(mg_sim* s, void* stream) {
     }
     // ---- end: the deferred sets were read (and the targets written through), the outputs written
     s->fuse.end_simulate(fs, cid);
+    // ---- sleeping: the pass over the islands, one launch per size class present
+    if (sleeping(s)) {
+        const MgLayout& L = s->layout;
+        const double window = s->sleep_window, tol = window * std::sqrt(2.0 * (double)s->sleep_threshold);
+        MgSleepArgs A{};
+        A.nb = L.nb; A.nd = L.nd;
+        A.window = (int)std::max(1l, std::lround(window / (double)s->params.dt));
+        A.tol2 = (float)(tol * tol);
+        A.body0 = s->sleep.d_body0; A.body = s->sleep.d_body; A.dof0 = s->sleep.d_dof0; A.dof = s->sleep.d_dof;
+        A.body_k = s->sleep.d_body_k;
+        A.state = s->d_state; A.dofs = s->d_dof;
+        A.timer = s->sleep.d_timer; A.asleep = s->sleep.d_asleep; A.anchor = s->sleep.d_anchor; A.dof_q = s->sleep.d_dof_q;
+        const int lanes[3] = {1, 16, 64};
+        for (int c = 0; c < 3; ++c) {
+            A.i0 = L.island_class0[c];
+            A.n = L.island_class0[c + 1] - L.island_class0[c];
+            HIP_TRY(mg_launch_sleep_pass(A, lanes[c], st));
+        }
+    }
     if (R.crep) {
         HIP_TRY(mg_launch_contact_compact(contact_args(s), st));
         s->crep_valid = true;
@@ -1151,6 +1243,9 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     in.attrs = host; in.n_attr = n;
     MgRoute R;
     if (int rc_ = plan_route(s->layout, in, R)) return rc_;
+    std::vector<int> wake;   // sleeping: the islands of the table's bodies
+    for (int i = 0; i < n; ++i)
+        if (s->layout.body_island[s->layout.perm[host[i].body]] >= 0) wake.push_back(s->layout.body_island[s->layout.perm[host[i].body]]);
     // the new state is built apart — fresh device buffers — and committed at the
     // end, so an error leaves the sim's table as it was
     DevBuf<int> d_idx, d_split;   // freed unless committed
@@ -1175,7 +1270,7 @@ int32_t mg_set_attractors(mg_sim* s, const mg_attractor* host, int32_t n) {
     s->attrs.assign(host, host + n);
     s->route = std::move(R);
     s->attr_dirty = n > 0;
-    return MG_OK;
+    return sleep_wake_sync(s, &wake);
 }
 
 int32_t mg_set_attractor_targets(mg_sim* s, const float* pose7, int32_t first, int32_t n) {
@@ -1191,14 +1286,17 @@ int32_t mg_set_attractor_targets(mg_sim* s, const float* pose7, int32_t first, i
         HIP_TRY(hipEventSynchronize(s->attr_ev));
         s->attr_ev_pending = false;
     }
+    std::vector<int> wake;   // sleeping: the islands of the moved attractors' bodies
     for (int i = 0; i < n; ++i) {
         mg_attractor& a = s->attrs[first + i];
         for (int k = 0; k < 3; ++k) a.target_p[k] = pose7[7 * i + k];
         for (int k = 0; k < 4; ++k) a.target_q[k] = pose7[7 * i + 3 + k];
         attr_record(a, s->h_attr + (size_t)(first + i) * MG_ATTR_N);
+        const int isl = s->layout.body_island[s->layout.perm[a.body]];
+        if (isl >= 0) wake.push_back(isl);
     }
     s->attr_dirty = true;
-    return MG_OK;
+    return sleep_wake_sync(s, &wake);
 }
 
 int32_t mg_num_attractors(mg_sim* s) { return s ? (int32_t)s->attrs.size() : 0; }
@@ -1262,6 +1360,87 @@ int32_t mg_joint_friction_stats(mg_sim* s, int32_t out[3]) {
     out[0] = s->route.jfr_ndof;
     out[1] = s->route.jfr_lanes;
     out[2] = s->route.jfr_envs;
+    return MG_OK;
+}
+
+// ---- sleeping ------------------------------------------------
+int32_t mg_set_sleeping(mg_sim* s, float threshold, float window) {
+    if (!s) return fail(MG_ERR_ARG, "null sim");
+    const bool on = std::isfinite(threshold) && std::isfinite(window) && threshold > 0.0f && window > 0.0f;
+    if (int rc_ = refuse_captured(s, "sleeping changed")) return rc_;
+    if (s->uploaded) {
+        HIP_TRY(hipSetDevice(s->device));
+        MgRouteIn in = route_in(s);
+        in.sleep = on;
+        MgRoute R;
+        if (int rc_ = plan_route(s->layout, in, R)) return rc_;
+        // fresh buffers, committed at the end: timers at 0, anchors taken at the next pass
+        SleepBufs B;
+        if (on)
+            if (int rc_ = sleep_alloc(s->layout, B)) return rc_;
+        HIP_TRY(hipDeviceSynchronize());   // no pass may still read the buffers this replaces
+        s->sleep = std::move(B);
+        s->route = std::move(R);
+    }
+    s->sleep_on = on;
+    s->sleep_threshold = on ? threshold : 0.0f;
+    s->sleep_window = on ? window : 0.0f;
+    return MG_OK;
+}
+
+int32_t mg_wake(mg_sim* s, const int32_t* actor_idx, int32_t n, int32_t idx_host, void* stream) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    if (actor_idx && n < 0) return fail(MG_ERR_ARG, "negative index count");
+    if (!sleeping(s) || (actor_idx && n == 0)) return MG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int* didx = actor_idx;
+    if (actor_idx && idx_host) {
+        if (int rc_ = ensure_stage(s, 0, (size_t)n)) return rc_;
+        const void* src[1] = {actor_idx};
+        const size_t bytes[1] = {(size_t)n * sizeof(int)};
+        void* dst[1] = {s->d_stage_idx};
+        if (int rc_ = pin_h2d(s, 1, src, bytes, dst, st)) return rc_;
+        didx = s->d_stage_idx;
+    }
+    return sleep_wake(s, didx, n, st);
+}
+
+int32_t mg_sleep_state(mg_sim* s, int32_t* dst, int32_t dst_host, void* stream) {
+    if (!s || !s->uploaded) return fail(MG_ERR_STATE, "sim has no uploaded model");
+    const int na = s->layout.na;
+    if (na == 0) return MG_OK;
+    if (!dst) return fail(MG_ERR_ARG, "null destination");
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!sleeping(s)) {   // nobody sleeps
+        if (dst_host) std::memset(dst, 0, (size_t)na * sizeof(int32_t));
+        else HIP_TRY(hipMemsetAsync(dst, 0, (size_t)na * sizeof(int32_t), st));
+        return MG_OK;
+    }
+    int* d = dst_host ? (int*)s->sleep.d_idx : dst;
+    HIP_TRY(mg_launch_sleep_actors(s->sleep.d_actor_island, na, s->sleep.d_asleep, d, st));
+    if (dst_host) {
+        HIP_TRY(hipMemcpyAsync(dst, d, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return MG_OK;
+}
+
+int32_t mg_sleep_stats(mg_sim* s, int32_t out[3]) {
+    if (!s) return fail(MG_ERR_ARG, "null sim");
+    if (!out) return fail(MG_ERR_ARG, "null output");
+    out[0] = out[1] = out[2] = 0;
+    if (!sleeping(s)) return MG_OK;
+    const MgLayout& L = s->layout;
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<int> asleep((size_t)L.n_island, 0);
+    HIP_TRY(hipDeviceSynchronize());
+    if (L.n_island > 0)
+        HIP_TRY(hipMemcpy(asleep.data(), s->sleep.d_asleep, asleep.size() * sizeof(int), hipMemcpyDeviceToHost));
+    out[0] = L.n_island;
+    for (int a : asleep) out[1] += a != 0 ? 1 : 0;
+    for (int c = 0; c < 3; ++c) out[2] += L.island_class0[c + 1] > L.island_class0[c] ? 1 : 0;
     return MG_OK;
 }
 
@@ -1402,7 +1581,7 @@ int32_t mg_debug_artic_groups(mg_sim* s, int32_t* out, int32_t cap) {
 // and no device — a window onto MgLayout (mg_layout.h)
 struct mg_layout {
     MgLayout L;
-    std::vector<int32_t> scalars;
+    std::vector<int32_t> scalars, island_class;
 };
 mg_layout* mg_debug_plan_layout(const mg_sim_params* p, const mg_model* m) {
     if (!p || !m) { fail(MG_ERR_ARG, "null argument"); return nullptr; }
@@ -1421,6 +1600,7 @@ mg_layout* mg_debug_plan_layout(const mg_sim_params* p, const mg_model* m) {
                                              g.offset, g.count, g.step_offset, g.step_count, g.uni_mass ? 1 : 0, g.nl});
     for (const MgEnvGroup& g : L.env_groups)
         h->scalars.insert(h->scalars.end(), {g.tmpl, g.wide, g.max_free, g.offset, g.count});
+    h->island_class = {L.n_island, L.island_class0[1], L.island_class0[2]};
     return h;
 }
 int32_t mg_debug_layout_table(const mg_layout* h, int32_t which, const void** data, int64_t* count) {
@@ -1441,6 +1621,14 @@ int32_t mg_debug_layout_table(const mg_layout* h, int32_t which, const void** da
         case MG_LAYOUT_CENV_ROW: return give(L.cenv_row);
         case MG_LAYOUT_CENV_CTAB_OFF: return give(L.cenv_ctab_off);
         case MG_LAYOUT_FREE_FLAGS: return give(L.free_flags);
+        case MG_LAYOUT_BODY_ISLAND: return give(L.body_island);
+        case MG_LAYOUT_ACTOR_ISLAND: return give(L.actor_island);
+        case MG_LAYOUT_ISLAND_BODY0: return give(L.island_body0);
+        case MG_LAYOUT_ISLAND_BODY: return give(L.island_body);
+        case MG_LAYOUT_ISLAND_DOF0: return give(L.island_dof0);
+        case MG_LAYOUT_ISLAND_DOF: return give(L.island_dof);
+        case MG_LAYOUT_ISLAND_CLASS: return give(h->island_class);
+        case MG_LAYOUT_BODY_K: return give(L.body_k);
         default: return fail(MG_ERR_ARG, "no layout table %d", which);
     }
 }
@@ -1722,6 +1910,8 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
     hipStream_t st = (hipStream_t)stream;
     const float* dsrc;
     const int* didx;
+    if (!idx)   // autowake: a full set wakes every island (an indexed one: below, its actors')
+        if (int rc_ = sleep_wake(s, nullptr, 0, st)) return rc_;
     const MgFusion::Set f = s->fuse.set_root(src, src_host, idx != nullptr, s->layout.roots_free, capture_id(st));
     if (int rc_ = apply_root(s, f.first, st)) return rc_;
     if (f.how != MG_SET_NOW) s->set_st[0] = st;
@@ -1746,6 +1936,7 @@ int32_t mg_set_actor_root_state(mg_sim* s, const float* src, int32_t src_host, c
     }
     int rc = stage_src(s, src, src_host, (size_t)s->layout.na * MG_STATE_N, idx, n_idx, st, &dsrc, &didx);
     if (rc) return rc;
+    if (idx && (rc = sleep_wake(s, didx, n_idx, st))) return rc;
     HIP_TRY(mg_launch_scatter_rows(dsrc, MG_STATE_N, s->d_actor_root, didx, idx ? n_idx : s->layout.na, s->layout.na,
                                    s->d_state, s->layout.nb, st));
     return MG_OK;
@@ -1759,6 +1950,7 @@ int32_t mg_set_rigid_body_state(mg_sim* s, const float* src, int32_t src_host, v
     const float* dsrc;
     const int* didx;
     if (int rc_ = apply_root(s, s->fuse.set_rigid_body(capture_id(st)), st)) return rc_;
+    if (int rc_ = sleep_wake(s, nullptr, 0, st)) return rc_;
     int rc = stage_src(s, src, src_host, (size_t)s->layout.nb * MG_STATE_N, nullptr, 0, st, &dsrc, &didx);
     if (rc) return rc;
     // free bodies only: rows are selected through the free-body list
@@ -1786,7 +1978,7 @@ static int32_t set_dof_target(mg_sim* s, int k, const float* src, int32_t src_ho
     if (int rc_ = apply_tgt(s, k, f.first, st)) return rc_;
     if (f.how == MG_SET_DEFER) {
         s->set_st[1 + k] = st;
-        return MG_OK;
+        return sleep_wake(s, nullptr, 0, st);   // autowake: a full set wakes every island
     }
     return set_dof_columns(s, src, src_host, 1, s->d_dof_tgt + (size_t)k * s->layout.nd, nullptr, idx, n_idx, st);
 }
@@ -1832,7 +2024,7 @@ int32_t mg_set_dof_props(mg_sim* s, const float* props_host) {
     for (size_t gi = 0; gi < s->groups.size(); ++gi)
         if (s->layout.groups[gi].uni_mass) chain_uni_dof(props_host, s->layout.groups[gi], s->groups[gi]);
     HIP_TRY(chain_uni_upload(s));
-    return MG_OK;
+    return sleep_wake_sync(s, nullptr);
 }
 
 int32_t mg_apply_rigid_body_force(mg_sim* s, const float* force, const float* torque, int32_t space,
@@ -1853,6 +2045,8 @@ int32_t mg_apply_rigid_body_force(mg_sim* s, const float* force, const float* to
         if (src_host) HIP_TRY(hipStreamSynchronize(st));  // staging buffer is reused by the next part
     }
     s->ext_pending = true;
+    if (sleeping(s))   // the islands of the bodies that now hold a force or a torque
+        HIP_TRY(mg_launch_wake_ext(s->d_ext, s->layout.nb, s->sleep.d_body_island, s->sleep.d_timer, s->sleep.d_asleep, st));
     return MG_OK;
 }
 

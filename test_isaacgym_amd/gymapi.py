@@ -23,6 +23,7 @@ import torch
 from . import _assets
 from . import _native as N
 from . import _render
+from . import _sim
 from ._sim import Actor, CameraSensor, Env, Sim, Viewer
 from ._types import *  # noqa: F401,F403
 from ._types import (_DOF_TYPE_STRINGS, _JOINT_TYPE_STRINGS, DOF_PROPERTIES_DTYPE, DofState, Quat,
@@ -1488,6 +1489,40 @@ class Gym:
 
     def get_rigid_contact_reporting(self, sim):
         return bool(sim.contact_reporting[0])
+
+    # ---- sleeping (include/migym.h)
+    def set_sleeping(self, sim, enabled=True, threshold=_sim.SLEEP_DEFAULTS[0], window=_sim.SLEEP_DEFAULTS[1]):
+        """migym extension (PhysX sleeping, which Isaac Gym has always on): an
+        island — the moving bodies of an env whose bodies can touch, else each
+        moving actor alone — that stays within window * sqrt(2 * threshold) (4 mm
+        by default) of where it was for `window` seconds falls asleep: its state
+        rows stay constant bit for bit and its velocities exactly 0 until it is
+        woken. Every state, DOF target or effort set wakes the actors it names
+        (all when not indexed), an applied force the bodies it pushes, a moved
+        attractor its body; wake_actors wakes by hand. threshold in m^2/s^2
+        (PhysX's sleepThreshold), window in seconds. Off by default; the
+        environment variable MIGYM_SLEEP (1, or threshold,window) turns it on for
+        new sims. Raises ValueError for values that are not finite and positive,
+        MigymError where the library refuses (after a simulate captured into a
+        graph)."""
+        sim.set_sleeping(bool(enabled), threshold, window)
+        return True
+
+    def get_sleeping(self, sim):
+        """None while sleeping is off, else (threshold, window)."""
+        return sim.sleeping
+
+    def get_sleeping_actors(self, sim):
+        """A bool array, one entry per actor of the sim (tensor-API actor order):
+        True while the actor's island is asleep. All False while sleeping is off."""
+        return sim.sleeping_actors()
+
+    def wake_actors(self, sim, indices=None):
+        """Wakes the islands of the actors `indices` (sim-domain actor indices: a
+        sequence, numpy array or torch tensor), or every island when None.
+        ValueError for an index out of range."""
+        sim.wake_actors(indices)
+        return True
 
     # ---- contact capacity report (include/migym.h, DESIGN.md §3.16)
     def get_contact_capacity_report(self, sim, reset=False):
